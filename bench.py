@@ -4,6 +4,11 @@
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times K steps and prints the headline (`value`, `ms_per_step`); the other lines of the result
+(`roofline`, `attn_fwd`, `decode`, `t128`, `f32`, `fed`, `cpu_baseline`, the step's host time in `executor`) are null unless
+`--full` is given, which measures them after the timed steps.  `--dump-outputs DIR` writes what the last timed step computed
+(bench.py:dump_outputs) so that two builds can be compared output for output: the inputs and initial weights are seeded.
+
 A *step* is one training step of the reference's loop (train.py:29-37: forward, pointer-generator
 log-probs, 4 label-smoothed losses, backward, Adam with the Noam rate) on one synthetic batch of
 BASELINE.json configs[1]: L=6, d_model=512, h=8, ResNeXt features [B=16, T=32, 7x7, 2048] bf16 already
@@ -166,6 +171,29 @@ def cpu_baseline(rows_wanted, threads):
     return out
 
 
+DUMP_WEIGHTS = 1 << 23               # float32 master weights written by --dump-outputs at most (32 MB)
+
+
+def dump_outputs(out_dir, terms, trainer):
+    """--dump-outputs: what the last timed step handed its caller -- the loss terms it returned (float64 scalars, loss_<name>.npy) and
+    the float32 master weights its Adam update wrote (master_weights.npy): all of them, or beyond DUMP_WEIGHTS a fixed sample, one
+    element per stride at a seeded offset inside the stride, so two runs of the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if trainer.master.is_cuda:
+        torch.cuda.synchronize()
+    for k, v in terms.items():
+        np.save(os.path.join(out_dir, f"loss_{k}.npy"), v.detach().double().cpu().numpy())
+    w = trainer.master
+    n = w.numel()
+    if n > DUMP_WEIGHTS:
+        stride = n // DUMP_WEIGHTS
+        offs = np.random.default_rng(0).integers(0, stride, DUMP_WEIGHTS)
+        idx = torch.from_numpy(np.arange(DUMP_WEIGHTS, dtype=np.int64) * stride + offs).to(w.device)
+        w = w[idx]
+    np.save(os.path.join(out_dir, "master_weights.npy"), w.detach().float().cpu().numpy())
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a torch.distributed.run child (this process has not
     touched the GPU) and leave with its exit code; rank 0 of the child writes the JSON line to our stdout."""
@@ -195,6 +223,12 @@ def main():
     ap.add_argument("--no-f32", action="store_true", help="skip the float32 side line (the same step in the parity dtype)")
     ap.add_argument("--no-fed", action="store_true", help="skip the PCIe-inclusive side line (features from host memory every step)")
     ap.add_argument("--no-graph", action="store_true", help="launch the kernels of a step eagerly instead of replaying a hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the step's host time, the roofline region, the decode turn, T=128, float32, the "
+                         "PCIe-inclusive step and the CPU baseline (the --no-* switches above trim this set); without it those lines are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0): its loss terms and a fixed sample of the "
+                         "float32 master weights it updated")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -266,22 +300,52 @@ def main():
             dist.barrier()
 
     def timed_steps(tr, bt, warm, steps):
+        """(seconds of the timed steps, the loss terms the last of them returned)"""
         for _ in range(warm):
             tr.step(bt)
         torch.cuda.synchronize(); barrier()
+        terms = None
         t0 = time.perf_counter()
         for _ in range(steps):
-            tr.step(bt)
+            terms = tr.step(bt)
         torch.cuda.synchronize(); barrier()
-        return time.perf_counter() - t0
+        return time.perf_counter() - t0, terms
 
-    dt = timed_steps(trainer, batch, a.warmup, a.steps)
+    dt, last_terms = timed_steps(trainer, batch, a.warmup, a.steps)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_terms, trainer)
+    del last_terms
     # what replayed the step: the split-graph executor (one single-queue hipGraph per stream, device-flag syncs) or the runtime's
     sp = getattr(trainer, "_split", None)
     executor = {"kind": "split" if sp is not None else ("runtime" if trainer.use_graph else "eager")}
     if sp is not None:
         executor.update({k: sp.info[k] for k in ("chains", "nodes", "waits", "signals", "nodes_per_chain")})
         executor["timed_out_waits"] = sp.errors()
+    tot = torch.tensor([dt, float(ntok)], device="cuda", dtype=torch.float64)
+    if world > 1:
+        tmax = tot.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        tsum = tot.clone(); dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
+        dt, ntok_all = float(tmax[0]), float(tsum[1])
+    else:
+        ntok_all = float(ntok)
+    out = {
+        "metric": "training-step tokens/sec (BiST hot path: fwd + pointer-generator losses + bwd + Adam)",
+        "value": ntok_all * a.steps / dt, "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: 6-layer d_model=512 nhead=8 MTN, synthetic ResNeXt feats "
+                               f"[B={c['B']}/GPU,T={c['T']},7x7,2048] {a.dtype} + 20-token queries, dropout={a.dropout}",
+                   "global_batch": c["B"] * world, "tokens_per_step": ntok_all, "parallelism": f"dp{world}",
+                   "clips_per_s": c["B"] * world * a.steps / dt},
+        "roofline": None, "attn_fwd": None, "executor": executor, "decode": None, "t128": None, "f32": None, "fed": None,
+    }
+    if rank == 0:
+        out["cpu_baseline"] = None
+    if not a.full:
+        finish(out, result_fd, rank, world)
+        return
+
+    # ---- --full: everything beyond the headline --------------------------------------------------------------------------------
     hs, ready, whole = [], [], []
     for _ in range(10):                           # host time of one step() call with the device idle (hipGraphLaunch and the loop around it)
         torch.cuda.synchronize(); h0 = time.perf_counter(); trainer.step(batch); hs.append((time.perf_counter() - h0) * 1e3)
@@ -297,13 +361,6 @@ def main():
                                 "bucket_ready_ms": [round(sorted(r[j] for r in ready)[len(ready) // 2] * 1e3, 2) for j in range(len(trainer.buckets))],
                                 "isolated_step_ms": round(sorted(whole)[len(whole) // 2], 2)}
         executor["host_ms_per_step"] = None       # (the host polls the buckets' flags inside step(): not a launch cost)
-    tot = torch.tensor([dt, float(ntok)], device="cuda", dtype=torch.float64)
-    if world > 1:
-        tmax = tot.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        tsum = tot.clone(); dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
-        dt, ntok_all = float(tmax[0]), float(tsum[1])
-    else:
-        ntok_all = float(ntok)
 
     # ---- the roofline region: P0 + one VidEncoderLayer4, inference, replayed from a hipGraph ------------------------------------
     model.eval()
@@ -421,7 +478,7 @@ def main():
         model.train()
         b128 = make_batch(c["B"], 128, 777)
         tr128 = Trainer(model, args, c["V"], compute_dtype=dtype, use_graph=not a.no_graph)
-        dt128 = timed_steps(tr128, b128, 3, 5)
+        dt128, _ = timed_steps(tr128, b128, 3, 5)
         model.eval()
         t128 = {"what": "BASELINE configs[3]: T=128 temporal segments, same model and batch size, training step and the roofline region",
                 "ms_per_step": dt128 / 5 * 1e3, "tokens_per_s": float(b128.ntokens.item()) * 5 / dt128, "attn_fwd": region_report(c["B"], 128, b128)}
@@ -434,7 +491,7 @@ def main():
         b32 = synthetic_batch(c["B"], T=c["T"], S=c["S"], C=c["C"], Lq=c["Lq"], Lh=c["Lh"], Lc=c["Lc"], Lt=c["Lt"], vocab=c["V"], seed=1234,
                               dtype=torch.float32)
         tr32 = Trainer(model, args, c["V"], compute_dtype=torch.float32, use_graph=not a.no_graph)
-        dt32 = timed_steps(tr32, b32, 2, 4)
+        dt32, _ = timed_steps(tr32, b32, 2, 4)
         model.eval()
         f32 = {"what": "the same training step with float32 operands and float32 kernels (the dtype of the 1e-3 parity tests); not the headline",
                "ms_per_step": dt32 / 4 * 1e3, "tokens_per_s": float(b32.ntokens.item()) * 4 / dt32}
@@ -470,15 +527,7 @@ def main():
                "ms_per_step": dtf / k * 1e3, "tokens_per_s": ntf / dtf, "h2d_bytes_per_step": int(host[0].fts.numel() * 4), "steps": k}
         del trf, it, host
 
-    out = {
-        "metric": "training-step tokens/sec (BiST hot path: fwd + pointer-generator losses + bwd + Adam)",
-        "value": ntok_all * a.steps / dt, "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": a.dtype, "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: 6-layer d_model=512 nhead=8 MTN, synthetic ResNeXt feats "
-                               f"[B={c['B']}/GPU,T={c['T']},7x7,2048] {a.dtype} + 20-token queries, dropout={a.dropout}",
-                   "global_batch": c["B"] * world, "tokens_per_step": ntok_all, "parallelism": f"dp{world}",
-                   "clips_per_s": c["B"] * world * a.steps / dt},
+    out.update({
         "roofline": {"bound": "mfma", "achieved": roof["tflops"], "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": roof["frac_of_mfma_peak"], "traffic": (traffic or {}).get("traffic_bytes"),
                      "traffic_detail": traffic if traffic is not None else {"note": traffic_note},
@@ -491,16 +540,20 @@ def main():
         "t128": t128,
         "f32": f32,
         "fed": fed,
-    }
+    })
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_rows, a.cpu_threads)
-    elif rank == 0:
-        out["cpu_baseline"] = None
+    finish(out, result_fd, rank, world)
+
+
+def finish(out, result_fd, rank, world):
+    """Rank 0 writes the result line to the saved stdout; the ranks leave together."""
     if rank == 0:
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if world > 1:
-        barrier()                              # rank 0 also ran the decode / B=64 extras: leave together
+        import torch.distributed as dist
+        dist.barrier()                         # rank 0 also ran the decode / B=64 extras: leave together
         dist.destroy_process_group()
     elif os.environ.get("BIST_BENCH_REHEARSAL") == "rccl1":
         import torch.distributed as dist1

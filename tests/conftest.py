@@ -3,7 +3,10 @@ import os
 # HIP runtime switches the split-graph executor needs (bist_amd/__init__.py), set before anything can initialise the runtime
 if os.environ.get("BIST_SPLIT_GRAPH", "1") != "0":
     os.environ.setdefault("DEBUG_HIP_DYNAMIC_QUEUES", "0")
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+    # raised, not defaulted: a launcher that exports the runtime's default of 4 would leave the split executor's tests without the
+    # hardware queues its chains need (bist_amd.graphsplit.usable() then refuses it and those tests fail)
+    if int(os.environ.get("GPU_MAX_HW_QUEUES", "0")) < 8:
+        os.environ["GPU_MAX_HW_QUEUES"] = "8"
     os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "1")
 import sys
 
