@@ -71,6 +71,18 @@ class BistStageJob(C.Structure):
                 ("pad", C.c_uint64), ("pad_bytes", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class BistTrainStage(C.Structure):
+    _fields_ = [("src", C.c_void_p * 5), ("dst", C.c_void_p * 5),
+                ("query_mask", C.c_void_p), ("query_mask2", C.c_void_p), ("his_mask", C.c_void_p), ("cap_mask", C.c_void_p),
+                ("trg_mask", C.c_void_p), ("trg_mean_mask", C.c_void_p), ("temporal_mask", C.c_void_p),
+                ("ntokens", C.c_void_p), ("qntokens", C.c_void_p), ("d_ntokens", C.c_void_p), ("d_qntokens", C.c_void_p),
+                ("fts", C.c_void_p), ("d_fts", C.c_void_p),
+                ("src_ld", C.c_int64 * 5), ("row_elems", C.c_int64), ("pad", C.c_int64),
+                ("src_len", C.c_int32 * 5), ("dst_len", C.c_int32 * 5),
+                ("B", C.c_int32), ("T", C.c_int32), ("PT", C.c_int32), ("fts_dtype", C.c_int32), ("out_dtype", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
 class BistLnBwdSet(C.Structure):
     _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("a", C.c_void_p), ("dx", C.c_void_p), ("da", C.c_void_p), ("db", C.c_void_p),
                 ("dx_add", C.c_void_p), ("dz", C.c_void_p), ("drop_row0", C.c_uint64)]
@@ -154,6 +166,7 @@ SIGNATURES = {
     "bist_text_vector_fwd": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P]),
     "bist_decoder_cache_fill": (C.c_int, [_P, _I32, _I32, _P]),
     "bist_stage_inputs": (C.c_int, [_P, _I32, _P]),
+    "bist_stage_train_batch": (C.c_int, [C.POINTER(BistTrainStage), _P]),
     "bist_xent_smooth_fwd": (C.c_int, [_P, _P, _I64, _I64, _I32, _F, _I32, _P, _P, _P]),
     "bist_xent_smooth_bwd": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _F, _I32, _P]),
     "bist_sum_div_groups": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _P]),

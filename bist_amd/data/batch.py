@@ -65,3 +65,32 @@ class Batch:
             if v is not None:
                 setattr(self, name, v.to("cuda", non_blocking=True))
         return self
+
+
+_DERIVED = ("query_mask", "query_mask2", "his_mask", "cap_mask", "trg_mask", "trg_mean_mask", "temporal_mask")
+
+
+class SourceBatch(Batch):
+    """A Batch whose derived fields -- the masks and ``temporal_mask`` -- are built on FIRST ACCESS only.  What the class-mode Trainer
+    reads of a batch is its ids, features and token counts: its staging launch (bist_stage_train_batch) derives every mask again, at
+    the class lengths.  A batch handed to it this way costs two token counts instead of ten mask launches and a pass of
+    bist_temporal_mask over the features, so a fed class step reads the features once.  Any other consumer sees a complete Batch."""
+
+    def __init__(self, query, his, fts, cap, trg, trg_y=None, pad: int = PAD, vids=None, qa_ids=None):
+        self.vids, self.qa_ids = vids, qa_ids
+        self.query, self.his, self.cap, self.trg, self.trg_y = query, his, cap, trg, trg_y
+        self.fts = fts
+        self.pad = pad
+        self.ntokens = (trg_y != pad).sum() if trg_y is not None else None   # dataset.py:98
+        self.qntokens = (query != pad).sum()                                  # dataset.py:99
+        self.audio_fts = None
+        self.audio_mask = None
+
+    def __getattr__(self, name):
+        # (called only for attributes not set yet: the derived fields, all at once, from the fields as they are now)
+        if name not in _DERIVED or "query" not in self.__dict__:
+            raise AttributeError(name)
+        full = Batch(self.query, self.his, self.fts, self.cap, self.trg, self.trg_y, pad=self.pad)
+        for f in _DERIVED:
+            self.__dict__.setdefault(f, getattr(full, f))
+        return self.__dict__[name]

@@ -21,6 +21,13 @@ bytes move:
   * ``temporal_mask`` is derived on the device from the features that just landed (``bist_temporal_mask``,
     bit-identical to dataset.py:79), so the host never reduces the feature tensor.
 
+Ragged batches (``length_classes=``, the class-mode ``Trainer``): every slot is one flat buffer per field that GROWS to the largest batch
+seen and never shrinks, and each batch is a view of its exact shape -- no allocation once the largest class has passed (without classes a
+change of shape re-allocates the field's pinned and device buffers: up to 205 MB per field and slot).  The features stay in the dtype they
+crossed PCIe in: the trainer's staging launch (``bist_stage_train_batch``) casts them on its way into the class-shaped static batch, and
+the yielded batch builds its masks and ``temporal_mask`` only if something reads them (``SourceBatch``; the staging launch derives its
+own), so a fed class step reads the features once instead of twice.
+
 Nothing here is on the timed path of ``bench.py``'s ``value`` (features resident in HBM, as the metric prescribes); its ``fed``
 side line is the PCIe-inclusive rate through this class.
 """
@@ -32,7 +39,7 @@ import torch
 
 from .._lib import check, lib
 from ..ops import dtype_code
-from .batch import PAD, Batch
+from .batch import PAD, Batch, SourceBatch
 
 _FIELDS = ("query", "his", "cap", "trg", "trg_y")
 
@@ -55,10 +62,13 @@ class DeviceFeeder:
     after the work queued on the consumer stream up to that point has finished).
     """
 
-    def __init__(self, source: Iterable[HostBatch], device="cuda", feature_dtype: torch.dtype = torch.bfloat16, pad: int = PAD):
+    def __init__(self, source: Iterable[HostBatch], device="cuda", feature_dtype: torch.dtype = torch.bfloat16, pad: int = PAD,
+                 length_classes=None):
         if not torch.cuda.is_available():
             raise RuntimeError("bist_amd.data.DeviceFeeder needs the MI355X (there is no CPU path)")
         self.source, self.device, self.feature_dtype, self.pad = source, torch.device(device), feature_dtype, pad
+        # length classes: grown flat buffers and exact-shape views; features handed over in their source dtype (see the module docstring)
+        self.length_classes = length_classes
         # The copy stream must not share a hardware QUEUE with a chain of the split-graph executor: its cast launch sits behind a 4 ms
         # host-to-device copy, and a chain queued behind THAT stands still for as long (measured: 17.5 ms per fed step from a pool stream,
         # 11.6 ms sharing the caption chain's queue, against 8.4 ms resident).
@@ -76,12 +86,29 @@ class DeviceFeeder:
 
     # -- staging ---------------------------------------------------------------------------------
     def _slot(self, table, name, like: torch.Tensor, dtype, pinned: bool):
+        if self.length_classes is not None:
+            return self._grown(table, name, like.shape, dtype, pinned)
         buf = table.get(name)
         if buf is None or buf.shape != like.shape or buf.dtype != dtype:
             buf = (torch.empty(like.shape, dtype=dtype, pin_memory=True) if pinned
                    else torch.empty(like.shape, dtype=dtype, device=self.device))
             table[name] = buf
         return buf
+
+    def _grown(self, table, name, shape, dtype, pinned: bool) -> torch.Tensor:
+        """An exact-shape view of the slot's flat buffer for `name`, grown (never shrunk) to hold it."""
+        n = 1
+        for s_ in shape:
+            n *= int(s_)
+        buf = table.get(name)
+        if buf is None or buf.dtype != dtype or buf.numel() < n:
+            buf = (torch.empty(n, dtype=dtype, pin_memory=True) if pinned else torch.empty(n, dtype=dtype, device=self.device))
+            table[name] = buf
+        return buf[:n].view(shape)
+
+    def capacity_bytes(self) -> int:
+        """Bytes of device and pinned slot buffers the feeder holds now."""
+        return sum(t.numel() * t.element_size() for tab in self._pinned + self._dev for t in tab.values())
 
     @staticmethod
     def pinned_like(shape, dtype) -> torch.Tensor:
@@ -125,7 +152,7 @@ class DeviceFeeder:
         self._in_flight = False
         dev = self._dev[slot]
         d = tensors["fts"]
-        if d is not None and d.dtype != self.feature_dtype:
+        if d is not None and d.dtype != self.feature_dtype and self.length_classes is None:
             c = self._slot(dev, "fts_cast", d, self.feature_dtype, False)
             check(lib.bist_cast(d.data_ptr(), c.data_ptr(), d.numel(), dtype_code(d.dtype), dtype_code(self.feature_dtype),
                                 torch.cuda.current_stream(self.device).cuda_stream), "bist_cast")
@@ -147,6 +174,8 @@ class DeviceFeeder:
             self._in_flight = False
 
     def _batch(self, tensors) -> Batch:
+        if self.length_classes is not None:      # masks on first access only: the class-mode Trainer derives its own (SourceBatch)
+            return SourceBatch(tensors["query"], tensors["his"], tensors["fts"], tensors["cap"], tensors["trg"], tensors["trg_y"], pad=self.pad)
         return Batch(tensors["query"], tensors["his"], tensors["fts"], tensors["cap"], tensors["trg"], tensors["trg_y"], pad=self.pad)
 
     # -- iteration -------------------------------------------------------------------------------

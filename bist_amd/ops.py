@@ -418,6 +418,68 @@ def stage_inputs(jobs) -> None:
         check(lib.bist_stage_inputs(arr, len(part), _stream()), "bist_stage_inputs")
 
 
+_TRAIN_IDS = ("query", "his", "cap", "trg", "trg_y")
+_TRAIN_MASKS = ("query_mask", "query_mask2", "his_mask", "cap_mask", "trg_mask", "trg_mean_mask", "temporal_mask")
+
+
+def stage_train_batch(src, dst, pad: int) -> None:
+    """bist_stage_train_batch: the exact-shape training batch `src` (a bist_amd.data.Batch) into the class-shaped batch `dst` whose
+    tensors are preallocated (ids int64 [B, P], masks bool in the shapes of Batch, fts [B, PT, S, C] in the compute dtype, ntokens /
+    qntokens int64 scalars; all contiguous): ids padded with `pad`, every mask derived from the staged ids / features, features cast.
+    One launch on the current stream; capturable."""
+    from ._lib import BistTrainStage
+    d = BistTrainStage()
+    B = src.query.shape[0]
+    for f, name in enumerate(_TRAIN_IDS):
+        s, t = getattr(src, name, None), getattr(dst, name, None)
+        if s is None:
+            continue
+        _dev(s, t)
+        if (t is None or s.dtype != torch.int64 or t.dtype != torch.int64 or s.dim() != 2 or s.stride(-1) != 1 or not t.is_contiguous()
+                or s.shape[0] != B or t.shape[0] != B or t.shape[1] < s.shape[1]):
+            raise ValueError(f"bist_amd.stage_train_batch: {name}: int64 [B, L] rows into a contiguous [B, P >= L]")
+        d.src[f], d.dst[f] = s.data_ptr(), t.data_ptr()
+        d.src_ld[f], d.src_len[f], d.dst_len[f] = s.stride(0), s.shape[1], t.shape[1]
+    f, g = src.fts, dst.fts
+    _dev(f, g)
+    if not f.is_contiguous() or not g.is_contiguous() or f.shape[0] != B or g.shape[0] != B or f.shape[2:] != g.shape[2:] or g.shape[1] < f.shape[1]:
+        raise ValueError("bist_amd.stage_train_batch: features [B, T, S, C] into a contiguous [B, PT >= T, S, C]")
+    Pq, Ph, Pt, PT = d.dst_len[0], d.dst_len[1], d.dst_len[3], g.shape[1]
+    Pc = d.dst_len[2] if src.cap is not None else 0
+    if src.trg_y is not None and d.dst_len[4] != Pt:
+        raise ValueError("bist_amd.stage_train_batch: trg and trg_y share one class length")
+    # the launch writes through raw pointers: every mask must have exactly the shape Batch gives it at the class lengths
+    want = {"query_mask": (B, 1, Pq), "query_mask2": (2 * B, 1, Pq), "his_mask": (B, 1, Ph), "cap_mask": (B, 1, Pc),
+            "trg_mask": (B, Pt, Pt), "trg_mean_mask": (B, Pt), "temporal_mask": (B, 1, PT)}
+    for name in _TRAIN_MASKS:
+        m = getattr(dst, name, None)
+        if name == "cap_mask" and src.cap is None or name == "trg_mean_mask" and src.trg_y is None:
+            continue
+        if m is None:
+            if name == "query_mask2":
+                continue
+            raise ValueError(f"bist_amd.stage_train_batch: {name} is required")
+        _dev(m)
+        if m.dtype != torch.bool or not m.is_contiguous() or tuple(m.shape) != want[name]:
+            raise ValueError(f"bist_amd.stage_train_batch: {name} must be a contiguous bool tensor of shape {want[name]}, got "
+                             f"{tuple(m.shape)} {m.dtype}")
+        setattr(d, name, m.data_ptr())
+    for name in ("ntokens", "qntokens"):
+        s, t = getattr(src, name, None), getattr(dst, name, None)
+        if s is not None:
+            _dev(s, t)
+            if t is None or s.dtype != torch.int64 or t.dtype != torch.int64 or s.numel() != 1 or t.numel() != 1:
+                raise ValueError(f"bist_amd.stage_train_batch: {name}: int64 scalars")
+            setattr(d, name, s.data_ptr())
+            setattr(d, "d_" + name, t.data_ptr())
+    d.fts, d.d_fts = f.data_ptr(), g.data_ptr()
+    d.row_elems = f[0, 0].numel()
+    d.pad = int(pad)
+    d.B, d.T, d.PT = B, f.shape[1], g.shape[1]
+    d.fts_dtype, d.out_dtype = dtype_code(f.dtype), dtype_code(g.dtype)
+    check(lib.bist_stage_train_batch(C.byref(d), _stream()), "bist_stage_train_batch")
+
+
 def _children_signature(mods) -> int:
     return sum(id(c) for m in mods for c in m._modules.values()) + len(mods)
 

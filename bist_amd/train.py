@@ -22,6 +22,7 @@ low-precision weights.  No per-parameter optimiser launches, no per-tensor colle
 """
 from __future__ import annotations
 
+import collections
 import copy
 import os
 import time
@@ -73,6 +74,23 @@ EARLY_REDUCTIONS = os.environ.get("BIST_EARLY_REDUCTIONS", "1") != "0"      # ..
 FLUSH_AT_0 = os.environ.get("BIST_FLUSH_AT_0", "1") != "0"      # ... and, reductions only, once more at the end of the layer stacks' backward (mark 0)
 EXCHANGE_TIMEOUT_S = float(os.environ.get("BIST_EXCHANGE_TIMEOUT_S", "20"))       # a bucket whose flags do not arrive within this raises
 EXCHANGE_CHUNKS = int(os.environ.get("BIST_EXCHANGE_CHUNKS", "4"))        # pieces of the flat gradient per step (multi-rank): all-reduce k+1 runs under Adam k
+# Length classes: captured steps kept per trainer (least recently used evicted).  Each holds its capture's memory pool -- measured
+# 2.1-2.5 GB per class at BASELINE configs[1] (B=16, bf16) -- so the default bounds the store near 20 GB; 200 ragged
+# AVSD-like batches met 11 classes, and eight slots replayed them without a single re-capture.  The bound holds for the split executor
+# (an evicted graph and its pool are freed).  Without it (self-test failed, BIST_SPLIT_GRAPH=0) a multi-stream graph is RETIRED on
+# eviction, not destroyed (functional.Graph.__del__): up to BIST_RETIRED_GRAPHS_MAX of them stay alive with their pools, which
+# graph_stats()["bytes"] does not count -- there, size max_graphs so that no class is evicted.
+MAX_GRAPHS = int(os.environ.get("BIST_MAX_GRAPHS", "8"))
+
+
+class _GraphEntry:
+    """A captured step of one length class: the graph(s), the class-shaped static batch they read, their loss terms."""
+    __slots__ = ("graph", "graph2", "batch", "terms", "split", "bytes")
+
+    def __init__(self, graph, graph2, batch, terms, nbytes: int):
+        self.graph, self.graph2, self.batch, self.terms = graph, graph2, batch, terms
+        self.split = graph.split
+        self.bytes = int(nbytes)
 
 
 def _round(n: int) -> int:
@@ -83,12 +101,23 @@ class Trainer:
     def __init__(self, model: torch.nn.Module, args, vocab_size: int, *, compute_dtype: torch.dtype = torch.bfloat16,
                  warmup: int = 4000, factor: float = 1.0, smoothing: float = 0.1, pad: int = 1,
                  betas=(0.9, 0.98), eps: float = 1e-9, process_group=None, use_graph: bool = False,
-                 deferred_adam: Optional[bool] = None):
+                 deferred_adam: Optional[bool] = None, length_classes=None, max_graphs: int = MAX_GRAPHS):
         self.model, self.args = model, args
         self.use_graph = use_graph
         self._graph = self._graph2 = self._graph_key = self._static_batch = self._static_terms = None
         self._split = self._split2 = None
         self._static_src = {}
+        # Ragged batches (use_graph=True): one captured step per LENGTH CLASS (bist_amd.data.classes), the least recently used of at
+        # most max_graphs kept; every step stages its batch into the class's static batch with one launch (bist_stage_train_batch).
+        # None: one graph keyed by the exact shape of every batch field (a new shape is a new capture).
+        self.length_classes = length_classes
+        self.max_graphs = int(max_graphs)
+        if self.max_graphs < 1:
+            raise ValueError("Trainer: max_graphs must be at least 1")
+        self._entries: "collections.OrderedDict[tuple, _GraphEntry]" = collections.OrderedDict()
+        self._gstats = {"captures": 0, "hits": 0, "evictions": 0}
+        self._warming = False                 # the eager warm-up passes of a capture run (they signal no bucket flags)
+        self._pad = pad
         self.compute_dtype = compute_dtype
         self.warmup, self.factor, self.betas, self.eps = warmup, factor, betas, eps
         self.pg = process_group
@@ -423,7 +452,10 @@ class Trainer:
         self._early_done = 0
         early = self._early_armed and Fn.fourth_stream() is not None and torch.cuda.is_current_stream_capturing()
         flush0 = {0} if (FLUSH_AT_0 and EARLY_REDUCTIONS) else set()
-        Fn.BUCKET_MARK = (({b_[0] for b_ in self.buckets}, self._bucket_ready) if self.overlap else
+        # (a capture's eager warm-up passes signal nothing: a flag they left at this step's number would let the first replay's bucket
+        # all-reduce start before the replay has made that bucket's gradients final)
+        Fn.BUCKET_MARK = (None if (self.overlap and self._warming) else
+                          ({b_[0] for b_ in self.buckets}, self._bucket_ready) if self.overlap else
                           ({b_[0] for b_ in self.buckets} | flush0, self._bucket_adam) if early else None)
         try:
             loss, terms = self.forward_loss(batch)
@@ -528,17 +560,38 @@ class Trainer:
         static inputs).  Warm-up runs on a side stream first, as graph capture requires.  Several ranks: TWO graphs, the
         cut where the big matrices' gradients are final, so that their all-reduce starts under the closing reductions."""
         batch = self._own_copy(batch)             # the graphs read trainer-owned buffers, never the caller's (a feeder slot is rewritten in flight)
+        graph, graph2, terms = self._record(batch)
+        self._split = graph.split
+        self._graph, self._graph2, self._graph_key, self._static_batch, self._static_terms = graph, graph2, key, batch, terms
+        self._static_src = {}
+
+    def _record(self, batch, measure: bool = False):
+        """Warm-up passes and the capture of one step reading `batch` -> (graph, graph2 or None, static loss terms).  measure: note the
+        allocator's reserved bytes just before the capture (graph_stats)."""
         graph = Fn.Graph(split=SPLIT_GRAPH and self.flat_grad.is_cuda)
         if graph.want_split and Fn._streams_ready():
             # the weight-gradient stream (BIST_WGRAD_STREAM=1) on a hardware queue of its own as well
             if self.wgrad_side_stream:
                 self._wgrad_stream = Fn.leaf_stream()
+        # Deferred optimiser: the update the last step left pending is applied NOW.  The warm-up passes below overwrite the gradient
+        # buffer it would read, and the new graph's head then finds nothing pending (flush() resets the device-side step to 0).
+        self.flush()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self.backward(batch)              # warm-up passes leave the weights alone
+        self._warming = True
+        try:
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    self.backward(batch)              # warm-up passes leave the weights alone
+        finally:
+            self._warming = False
         torch.cuda.current_stream().wait_stream(side)
+        if measure:
+            # (torch.cuda.graph releases the allocator's unused cache as the capture begins: released here first, the growth of the
+            # reserved bytes across the capture is the graph's private pool alone)
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            self._held_before_capture = torch.cuda.memory_reserved(self.flat_grad.device)
         graph2 = None
         if self.exchanging:
             with Fn.capture_graph(graph):   # other threads (RCCL watchdog) may touch the runtime during capture
@@ -553,9 +606,7 @@ class Trainer:
                     terms = self.backward(batch, optimizer=self.adam_in_step)
             finally:
                 self._skip_head_clear = False
-        self._split = graph.split
-        self._graph, self._graph2, self._graph_key, self._static_batch, self._static_terms = graph, graph2, key, batch, terms
-        self._static_src = {}
+        return graph, graph2, terms
 
     def _globally_normalised(self, batch):
         """The reference normalises each loss term by the token count of the WHOLE batch (optimize.py:48-50: ``/ batch.ntokens``,
@@ -586,7 +637,87 @@ class Trainer:
         BIST_ALWAYS_COPY_INPUTS=1."""
         self._static_src.clear()
 
+    # ---- length classes: a bounded store of captured steps, one per class -------------------------------------------------
+    def _class_batch(self, batch):
+        """Trainer-owned, class-shaped buffers for every field of `batch` (features in the compute dtype; contents: staged later)."""
+        shp = self.length_classes.shape(batch)
+        B, dev = batch.query.shape[0], batch.query.device
+        own = copy.copy(batch)
+
+        def ids(P):
+            return torch.empty(B, P, dtype=torch.int64, device=dev)
+
+        def mask(*s_):
+            return torch.empty(*s_, dtype=torch.bool, device=dev)
+        Pq, Ph, Pc, Pt, PT = shp["query"], shp["his"], shp["cap"], shp["trg"], shp["frames"]
+        own.query, own.his, own.trg = ids(Pq), ids(Ph), ids(Pt)
+        own.cap = ids(Pc) if batch.cap is not None else None
+        own.trg_y = ids(Pt) if batch.trg_y is not None else None
+        own.fts = torch.empty((B, PT) + tuple(batch.fts.shape[2:]), dtype=self.compute_dtype, device=dev)
+        own.query_mask, own.query_mask2, own.his_mask = mask(B, 1, Pq), mask(2 * B, 1, Pq), mask(B, 1, Ph)
+        own.cap_mask = mask(B, 1, Pc) if batch.cap is not None else None
+        own.trg_mask, own.temporal_mask = mask(B, Pt, Pt), mask(B, 1, PT)
+        own.trg_mean_mask = mask(B, Pt) if batch.trg_y is not None else None
+        own.ntokens = torch.zeros((), dtype=torch.int64, device=dev) if batch.ntokens is not None else None
+        own.qntokens = torch.zeros((), dtype=torch.int64, device=dev)
+        return own
+
+    def _stage(self, batch, static) -> None:
+        """bist_stage_train_batch of `batch` into a class's static batch.  The launch reads contiguous features and unit-stride id rows; a
+        batch in another layout (features sliced out of a larger tensor, say) is made contiguous first -- one more pass over its bytes."""
+        src = batch
+        if not batch.fts.is_contiguous() or any(t is not None and t.stride(-1) != 1 for t in (batch.query, batch.his, batch.cap,
+                                                                                             batch.trg, batch.trg_y)):
+            src = copy.copy(batch)
+            for f in ("query", "his", "cap", "trg", "trg_y", "fts"):
+                t = getattr(batch, f, None)
+                if t is not None:
+                    setattr(src, f, t.contiguous())
+        ops.stage_train_batch(src, static, self._pad)
+
+    def _capture_class(self, batch, key) -> "_GraphEntry":
+        while len(self._entries) >= self.max_graphs:
+            # (a graph of the evicted class may still be running: its memory pool goes back to the allocator only after it is over)
+            torch.cuda.synchronize()
+            self._entries.popitem(last=False)
+            self._gstats["evictions"] += 1
+        self._graph = self._graph2 = self._static_batch = self._static_terms = None
+        static = self._class_batch(batch)
+        self._stage(batch, static)                                 # the warm-up passes read the staged batch
+        graph, graph2, terms = self._record(static, measure=True)
+        nbytes = torch.cuda.memory_reserved(static.fts.device) - self._held_before_capture + sum(
+            t.numel() * t.element_size() for t in (getattr(static, f, None) for f in self._BATCH_FIELDS) if t is not None)
+        ent = self._entries[key] = _GraphEntry(graph, graph2, static, terms, nbytes)
+        self._gstats["captures"] += 1
+        return ent
+
+    def _graph_open_classes(self, batch):
+        key = self.length_classes.key(batch)
+        ent = self._entries.get(key)
+        if ent is None:
+            ent = self._capture_class(batch, key)
+        else:
+            self._entries.move_to_end(key)
+            self._gstats["hits"] += 1
+        self._graph, self._graph2, self._graph_key, self._static_batch, self._static_terms = ent.graph, ent.graph2, key, ent.batch, ent.terms
+        self._split = ent.split
+        self._stage(batch, ent.batch)                              # one launch on the step's stream, right before the replay
+        if self._dirty and self.adam_in_step:
+            self.flat_grad.zero_()
+        self._dirty = False
+        ent.graph.replay()
+        return ent.terms
+
+    def graph_stats(self) -> Dict[str, int]:
+        """Length classes: captures, hits (replays of a stored class), evictions, classes held, and the device bytes they hold (each
+        entry: its capture's growth of the allocator's reserved memory -- the graph's private pool -- plus its static batch).  Evicted graphs
+        that the fallback executor retires instead of destroying (see MAX_GRAPHS) are not counted."""
+        return dict(self._gstats, entries=len(self._entries), bytes=sum(e.bytes for e in self._entries.values()),
+                    max_graphs=self.max_graphs)
+
     def _graph_open(self, batch):
+        if self.length_classes is not None:
+            return self._graph_open_classes(batch)
         if ALWAYS_COPY_INPUTS:
             self._static_src.clear()
         key = self._shape_key(batch)

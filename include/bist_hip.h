@@ -633,6 +633,30 @@ typedef struct BistStageJob {
 int bist_stage_inputs(const BistStageJob* jobs, int32_t n_jobs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A training batch of EXACT shape staged into the CLASS-shaped static batch of a captured step (bist_amd/train.py, length classes;
+ * the reference's collate_fn pads every batch to its own maxima, data/dataset.py:133-195) as ONE launch (csrc/stage_train.hip):
+ *   ids      field f of {query, his, cap, trg, trg_y}: int64 src[f] [B, src_len[f]] (row stride src_ld[f] elements) -> dst[f]
+ *            [B, dst_len[f]] contiguous, the tail filled with `pad`; a null src[f] (no caption, no trg_y) skips the field;
+ *   masks    DERIVED from the staged ids, never copied (dataset.py:66-67, 92, 96-98): query_mask [B,1,Pq], query_mask2 [2B,1,Pq]
+ *            (the same rows twice), his_mask [B,1,Ph], cap_mask [B,1,Pc], trg_mask [B,Pt,Pt] (pad AND causal), trg_mean_mask [B,Pt];
+ *            bool bytes; ntokens / qntokens (int64 scalars) are copied (padding adds no token);
+ *   features fts [B,T,row_elems] (fts_dtype f32 / bf16, contiguous) -> d_fts [B,PT,row_elems] in out_dtype with the rounding of
+ *            bist_cast, zero rows appended from T to PT; temporal_mask [B,1,PT] bit-identical to bist_temporal_mask over d_fts (the
+ *            same per-row summation order); 16-byte vectors: row_elems a multiple of 16 / sizeof(out dtype), 16-byte aligned rows.
+ * No allocation, no host synchronisation: capturable.  Unused mask pointers may be null.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct BistTrainStage {
+  const void* src[5]; void* dst[5];
+  void* query_mask; void* query_mask2; void* his_mask; void* cap_mask; void* trg_mask; void* trg_mean_mask; void* temporal_mask;
+  const void* ntokens; const void* qntokens; void* d_ntokens; void* d_qntokens;
+  const void* fts; void* d_fts;
+  int64_t src_ld[5]; int64_t row_elems; int64_t pad;
+  int32_t src_len[5]; int32_t dst_len[5];
+  int32_t B; int32_t T; int32_t PT; int32_t fts_dtype; int32_t out_dtype; int32_t reserved_;
+} BistTrainStage;
+int bist_stage_train_batch(const BistTrainStage* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Replay of a captured multi-stream hipGraph as ONE LINEAR GRAPH PER STREAM (csrc/graphsplit.hip).
  *
  * The reference runs its step as eager PyTorch launches on one stream (train.py:29-37; there is no graph or executor in the
