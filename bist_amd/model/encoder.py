@@ -249,6 +249,41 @@ class VidEncoderLayer4(nn.Module):
             ctx = Fn.scaled_bias(ctx, rowsum, attn.linears[2].bias, h)
         return Fn.linear(ctx, attn.linears[3].weight, attn.linears[3].bias, residual=xr, out_shape=(B, Lq, d), **Fn.drop_args(sub))
 
+    def _value_pack(self):
+        """[W_v(A1); W_v(A4)] and the packed bias for the one-GEMM inference value projection, re-packed INTO the same buffers (captured
+        hipGraphs keep reading them) whenever the parameters changed -- in place (optimizer.step, load_state_dict: _version) or behind
+        autograd's back (Trainer: ops.WEIGHTS_EPOCH)."""
+        a1, a4 = self.attn[1], self.attn[4]
+        key = ops.weights_key(a1.linears[2].weight, a4.linears[2].weight, a1.linears[2].bias, a4.linears[2].bias)
+        hit = self.__dict__.get("_vpack")
+        if hit is None or hit[0] != key:
+            same = hit is not None and hit[1].device == a1.linears[2].weight.device and hit[1].dtype == a1.linears[2].weight.dtype
+            w_new = Fn.pack_rows(a1.linears[2].weight, a4.linears[2].weight)
+            b_new = Fn.pack_rows(a1.linears[2].bias, a4.linears[2].bias)
+            if same:
+                hit[1].copy_(w_new); hit[2].copy_(b_new)
+                hit = (key, hit[1], hit[2])
+            else:
+                hit = (key, w_new, b_new)
+            self.__dict__["_vpack"] = hit
+        return hit[1], hit[2]
+
+    def refresh_derived(self, frag_jobs: list) -> None:
+        """Bring the derived inference operands this layer HOLDS up to the parameters' present values, in the buffers they already live
+        in: the packed value projection here, the fragment-ordered W_v / W_o as jobs (cache, attention, new key, [W_v, W_o], [buffers])
+        appended to `frag_jobs` for the caller to pack in one launch over all layers; the caller stores the new key once that launch
+        has gone out (ops.refresh_inference_operands).  A forward pass does the same on its way -- but a REPLAYED forward pass runs no
+        Python, so whoever replays one calls this after a weight update."""
+        cache = self.__dict__.get("_frag_cache") or {}
+        for ai, hit in list(cache.items()):
+            wv, wo = self.attn[ai].linears[2].weight, self.attn[ai].linears[3].weight
+            key = ops.weights_key(wv, wo)
+            if hit[0] != key and hit[1].device == wv.device and hit[1].dtype == wv.dtype:
+                frag_jobs.append((cache, ai, key, [wv.detach(), wo.detach()], [hit[1], hit[2]]))
+        if self.__dict__.get("_vpack") is not None:
+            with torch.no_grad():
+                self._value_pack()
+
     def value_projection(self, vft: Tensor):
         """V of A1 and A4 in one GEMM over the video tensor: returns (v_t2s, v_s2t) column views."""
         both = self.args.t2s and self.args.s2t
@@ -260,21 +295,7 @@ class VidEncoderLayer4(nn.Module):
                 return (Fn.linear(x2, a1.linears[2].weight, a1.linears[2].bias).view(B, T, S, d),
                         Fn.linear(x2, a4.linears[2].weight, a4.linears[2].bias).view(B, T, S, d))
             else:
-                key = ops.weights_key(a1.linears[2].weight, a4.linears[2].weight, a1.linears[2].bias, a4.linears[2].bias)
-                hit = self.__dict__.get("_vpack")
-                if hit is None or hit[0] != key:
-                    # re-packed INTO the same buffers (captured hipGraphs keep reading them) whenever the parameters changed --
-                    # in place (optimizer.step, load_state_dict: _version) or behind autograd's back (Trainer: ops.WEIGHTS_EPOCH)
-                    same = hit is not None and hit[1].device == a1.linears[2].weight.device and hit[1].dtype == a1.linears[2].weight.dtype
-                    w_new = Fn.pack_rows(a1.linears[2].weight, a4.linears[2].weight)
-                    b_new = Fn.pack_rows(a1.linears[2].bias, a4.linears[2].bias)
-                    if same:
-                        hit[1].copy_(w_new); hit[2].copy_(b_new)
-                        hit = (key, hit[1], hit[2])
-                    else:
-                        hit = (key, w_new, b_new)
-                    self.__dict__["_vpack"] = hit
-                w, bb = hit[1], hit[2]
+                w, bb = self._value_pack()
             v = Fn.linear(vft.view(B * T * S, d), w, bb).view(B, T, S, 2 * d)
             return v[..., :d], v[..., d:]
         a = self.attn[1]

@@ -480,6 +480,24 @@ def stage_train_batch(src, dst, pad: int) -> None:
     check(lib.bist_stage_train_batch(C.byref(d), _stream()), "bist_stage_train_batch")
 
 
+def eval_accumulate(terms: Sequence[Tensor], term_counts: Sequence[Tensor], counts: Sequence[Tensor], totals: Tensor,
+                    count_totals: Tensor) -> None:
+    """bist_eval_accumulate: totals[k] += terms[k] * term_counts[k] (f32 scalars times int64 scalars, summed in double),
+    count_totals[j] += counts[j], count_totals[len(counts)] += 1 (batches).  One launch on the current stream; capturable."""
+    _dev(*terms, *term_counts, *counts, totals, count_totals)
+    n, nc = len(terms), len(counts)
+    if (len(term_counts) != n or any(t.dtype != torch.float32 or t.numel() != 1 for t in terms)
+            or any(c.dtype != torch.int64 or c.numel() != 1 for c in (*term_counts, *counts))
+            or totals.dtype != torch.float64 or not totals.is_contiguous() or totals.numel() < n
+            or count_totals.dtype != torch.int64 or not count_totals.is_contiguous() or count_totals.numel() < nc + 1):
+        raise ValueError("bist_amd.eval_accumulate: f32 scalar terms, int64 scalar counts, float64 totals [>= terms], int64 count totals "
+                         "[>= counts + 1]")
+    a = (C.c_void_p * n)(*[t.data_ptr() for t in terms])
+    b = (C.c_void_p * n)(*[c.data_ptr() for c in term_counts])
+    c_ = (C.c_void_p * max(nc, 1))(*[c.data_ptr() for c in counts])
+    check(lib.bist_eval_accumulate(a, b, n, c_, nc, totals.data_ptr(), count_totals.data_ptr(), _stream()), "bist_eval_accumulate")
+
+
 def _children_signature(mods) -> int:
     return sum(id(c) for m in mods for c in m._modules.values()) + len(mods)
 
@@ -499,6 +517,29 @@ def module_parameters(root) -> list:
     """The Parameter objects under `root` as they are NOW (a replaced Parameter is seen: the modules' dicts are read at every call), without
     nn.Module.parameters()' recursive generators -- 0.3 instead of 1.7 ms for the whole model, paid at the head of every decode turn."""
     return [p for m in _module_list(root) for p in m._parameters.values() if p is not None]
+
+
+def refresh_inference_operands(root) -> int:
+    """The derived inference operands that a captured forward pass of bist_amd.train.Trainer reads -- the fragment-ordered W_v / W_o and
+    the packed value projection of every reasoning layer (model/encoder.py) -- brought up to the parameters' present values IN THE
+    BUFFERS THEY LIVE IN, so that a graph that baked those addresses computes with the new weights.  Eager launches on the current
+    stream; the fragment re-packs of all layers go out as one launch per 32 matrices (bist_pack_frag_rows_multi), and a layer's cache
+    is marked current only after its launch was issued without error.  Returns the number of matrices re-packed into fragment order.
+    (The other weights_key caches are not read by such a graph: packed Q/K/V projections are views of the parameters under a Trainer,
+    the decoder's stacked memory projections and descriptors belong to the decode-step launch of beam search.)"""
+    jobs = []                         # (cache dict, attention index, new key, [W_v, W_o], [their buffers])
+    for m in _module_list(root):
+        fn = getattr(m, "refresh_derived", None)
+        if fn is not None:
+            fn(jobs)
+    groups = {}
+    for job in jobs:
+        groups.setdefault((tuple(job[3][0].shape), job[3][0].dtype), []).append(job)
+    for part in groups.values():
+        pack_frag_rows_multi([w for j in part for w in j[3]], [o for j in part for o in j[4]])
+        for cache, ai, key, _, outs in part:
+            cache[ai] = (key, outs[0], outs[1])
+    return sum(len(j[3]) for j in jobs)
 
 
 def pack_frag_rows(w: Tensor, out: Optional[Tensor] = None) -> Tensor:

@@ -23,6 +23,7 @@ low-precision weights.  No per-parameter optimiser launches, no per-tensor colle
 from __future__ import annotations
 
 import collections
+import contextlib
 import copy
 import os
 import time
@@ -81,6 +82,15 @@ EXCHANGE_CHUNKS = int(os.environ.get("BIST_EXCHANGE_CHUNKS", "4"))        # piec
 # eviction, not destroyed (functional.Graph.__del__): up to BIST_RETIRED_GRAPHS_MAX of them stay alive with their pools, which
 # graph_stats()["bytes"] does not count -- there, size max_graphs so that no class is evicted.
 MAX_GRAPHS = int(os.environ.get("BIST_MAX_GRAPHS", "8"))
+# Forward-only class graphs of Trainer.eval_step / evaluate, in a store of their own (validation never evicts a training class).  An
+# entry keeps no activations for a backward pass: measured 0.21-0.28 GB per class at BASELINE configs[1] (B=16, bf16; 2.53 GB for the 11
+# classes of the 200-batch run, profiles/eval_classes_v1.json) against 2.1-2.5 GB of a training entry.  Sixteen
+# slots hold those 11 classes without an eviction, with room for a short last batch and a few rarer geometries, and bound the store
+# near 4.5 GB at that size (1.6 % of HBM).
+MAX_EVAL_GRAPHS = 16
+# bist_eval_accumulate (include/bist_hip.h): at most BIST_EVAL_MAX_TERMS = 8 running totals per loss term; the integer totals are the
+# two token counts handed over (of at most BIST_EVAL_MAX_COUNTS = 4) plus the batch counter the launch appends: tokens, qtokens, batches
+EVAL_TERMS_MAX, EVAL_COUNTS = 8, 3
 
 
 class _GraphEntry:
@@ -101,7 +111,8 @@ class Trainer:
     def __init__(self, model: torch.nn.Module, args, vocab_size: int, *, compute_dtype: torch.dtype = torch.bfloat16,
                  warmup: int = 4000, factor: float = 1.0, smoothing: float = 0.1, pad: int = 1,
                  betas=(0.9, 0.98), eps: float = 1e-9, process_group=None, use_graph: bool = False,
-                 deferred_adam: Optional[bool] = None, length_classes=None, max_graphs: int = MAX_GRAPHS):
+                 deferred_adam: Optional[bool] = None, length_classes=None, max_graphs: int = MAX_GRAPHS,
+                 max_eval_graphs: int = MAX_EVAL_GRAPHS):
         self.model, self.args = model, args
         self.use_graph = use_graph
         self._graph = self._graph2 = self._graph_key = self._static_batch = self._static_terms = None
@@ -116,6 +127,13 @@ class Trainer:
             raise ValueError("Trainer: max_graphs must be at least 1")
         self._entries: "collections.OrderedDict[tuple, _GraphEntry]" = collections.OrderedDict()
         self._gstats = {"captures": 0, "hits": 0, "evictions": 0}
+        # Validation (eval_step / evaluate): forward-only captured steps per length class, least recently used of at most max_eval_graphs
+        self.max_eval_graphs = int(max_eval_graphs)
+        if self.max_eval_graphs < 1:
+            raise ValueError("Trainer: max_eval_graphs must be at least 1")
+        self._eval_entries: "collections.OrderedDict[tuple, _GraphEntry]" = collections.OrderedDict()
+        self._estats = {"captures": 0, "hits": 0, "evictions": 0}
+        self._eval_weights_key = None         # the parameter values the derived inference operands were last refreshed for
         self._warming = False                 # the eager warm-up passes of a capture run (they signal no bucket flags)
         self._pad = pad
         self.compute_dtype = compute_dtype
@@ -293,6 +311,9 @@ class Trainer:
         self._main_stream = None
         self.criterion = LabelSmoothing(vocab_size, pad, smoothing)
         self.loss_compute = SimpleLossCompute(model.generator, model.ae_generator, self.criterion, opt=None, args=args)
+        # running totals of a validation pass, written by the tail launch of every evaluation step (bist_eval_accumulate)
+        self._eval_totals = torch.zeros(EVAL_TERMS_MAX, device=dev, dtype=torch.float64)
+        self._eval_counts = torch.zeros(EVAL_COUNTS, device=dev, dtype=torch.int64)
 
     # NoamOpt.rate (optimize.py:28-34)
     def rate(self, step: Optional[int] = None) -> float:
@@ -714,6 +735,157 @@ class Trainer:
         that the fallback executor retires instead of destroying (see MAX_GRAPHS) are not counted."""
         return dict(self._gstats, entries=len(self._entries), bytes=sum(e.bytes for e in self._entries.values()),
                     max_graphs=self.max_graphs)
+
+    # ---- validation: forward-only captured steps per length class, epoch totals on the device ---------------------------------
+    def _term_names(self) -> List[str]:
+        """The loss terms of this model, in the order SimpleLossCompute.terms returns them (optimize.py:50-82)."""
+        a = self.args
+        names = ["out"]
+        if a.auto_encoder:
+            if a.nb_cenc_blocks > 0:
+                names.append("cap_ae")
+            if a.nb_venc_blocks > 0 and a.enc_st_combine == "none":
+                names += (["temporal_ae"] if a.s2t else []) + (["spatial_ae"] if a.t2s else [])
+        return names
+
+    @contextlib.contextmanager
+    def _evaluating(self):
+        """The state of the reference's validation half (train.py:168-171: model.eval(), no autograd) around eval_step / evaluate: a
+        pending deferred update applied first, the model in eval mode and back in the mode it was found in afterwards, and the derived
+        inference operands the captured forward passes read brought up to the present weights (ops.refresh_inference_operands: once
+        per weight change, ahead of the first replay).  The decoder's per-turn reasoning cache stays off: it serves beam search, where
+        one dialogue is decoded step by step, and would route a one-dialogue batch through the decode-step launch and its per-turn
+        buffers."""
+        self.flush()
+        was = self.model.training
+        dec = getattr(self.model, "mutlimodal_decoder", None)
+        own_flag = dec is not None and "REASONING_CACHE" in dec.__dict__
+        prev_flag = dec.__dict__.get("REASONING_CACHE") if own_flag else None
+        self.model.eval()
+        if dec is not None and hasattr(dec, "REASONING_CACHE"):
+            dec.REASONING_CACHE = False
+        try:
+            with torch.no_grad():
+                if self.flat_param.is_cuda:
+                    key = (ops.WEIGHTS_EPOCH, sum(p._version for p in self.params))
+                    if key != self._eval_weights_key:
+                        ops.refresh_inference_operands(self.model)
+                        self._eval_weights_key = key
+                yield
+        finally:
+            if dec is not None:
+                if own_flag:
+                    dec.REASONING_CACHE = prev_flag
+                else:
+                    dec.__dict__.pop("REASONING_CACHE", None)
+            self.model.train(was)
+
+    def _eval_terms(self, batch):
+        ft = self.model.forward(batch)
+        terms, _ = self.loss_compute.terms(ft, batch)
+        if list(terms) != self._term_names():
+            raise RuntimeError("bist_amd.Trainer: loss terms %s, expected %s" % (list(terms), self._term_names()))
+        return terms
+
+    def _eval_accumulate(self, terms, batch) -> None:
+        """The tail launch of an evaluation step: term * count into the running totals, the counts and the batch into theirs."""
+        nt, qn = batch.ntokens, batch.qntokens
+        ops.eval_accumulate([t.detach() for t in terms.values()], [nt if k == "out" else qn for k in terms], [nt, qn],
+                            self._eval_totals, self._eval_counts)
+
+    def _capture_eval(self, batch, key) -> "_GraphEntry":
+        """Warm-up passes and the capture of the forward-only step of one class: model.forward in eval mode, the loss terms and the
+        accumulation launch in ONE graph (no backward, no optimiser, nothing that moves `drop_ctr`, the gradient or the Adam state)."""
+        while len(self._eval_entries) >= self.max_eval_graphs:
+            # (a graph of the evicted class may still be running: its memory pool goes back to the allocator only after it is over)
+            torch.cuda.synchronize()
+            self._eval_entries.popitem(last=False)
+            self._estats["evictions"] += 1
+        static = self._class_batch(batch)
+        self._stage(batch, static)                                 # the warm-up passes read the staged batch
+        graph = Fn.Graph(split=SPLIT_GRAPH and self.flat_param.is_cuda)
+        if graph.want_split:
+            Fn._streams_ready()                                    # (the split executor's streams exist before the warm-up passes pick theirs)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._eval_terms(static)                           # (they also build the derived operands of this geometry's kernel forms)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()                                   # (as in _record: the growth across the capture is the graph's pool alone)
+        held = torch.cuda.memory_reserved(static.fts.device)
+        with Fn.capture_graph(graph):
+            terms = self._eval_terms(static)
+            Fn.join_side_streams()
+            self._eval_accumulate(terms, static)
+        nbytes = torch.cuda.memory_reserved(static.fts.device) - held + sum(
+            t.numel() * t.element_size() for t in (getattr(static, f, None) for f in self._BATCH_FIELDS) if t is not None)
+        ent = self._eval_entries[key] = _GraphEntry(graph, None, static, terms, nbytes)
+        self._estats["captures"] += 1
+        return ent
+
+    def _eval_open(self, batch):
+        """One evaluation batch inside _evaluating(): staged into its class's static batch and replayed, or -- without use_graph and
+        length classes -- the same computation as eager launches."""
+        if hasattr(batch, "move_to_cuda") and not batch.query.is_cuda and self.flat_param.is_cuda:
+            batch.move_to_cuda()
+        if not (self.use_graph and self.length_classes is not None and batch.query.is_cuda):
+            terms = self._eval_terms(batch)
+            self._eval_accumulate(terms, batch)
+            return terms
+        key = self.length_classes.key(batch)
+        ent = self._eval_entries.get(key)
+        if ent is None:
+            ent = self._capture_eval(batch, key)
+        else:
+            self._eval_entries.move_to_end(key)
+            self._estats["hits"] += 1
+        self._stage(batch, ent.batch)                              # one launch on the step's stream, right before the replay
+        ent.graph.replay()
+        return ent.terms
+
+    def eval_step(self, batch) -> Dict[str, torch.Tensor]:
+        """One validation batch: forward pass and loss terms with dropout off -- no backward, no optimiser; the step counter, the
+        dropout counter, the gradient buffer and the Adam state stay as they are.  Returns the keys of step() as detached device scalars,
+        each divided by its token count (SimpleLossCompute.terms); no host synchronisation.  With use_graph and length classes the
+        tensors are the class entry's static outputs: the next evaluation of that class overwrites them.  Without them the same
+        computation runs as eager launches -- on the device: like every operator of this build, the accumulation launch has no host path."""
+        with self._evaluating():
+            return {k: v.detach() for k, v in self._eval_open(batch).items()}
+
+    def evaluate(self, batches) -> Dict[str, float]:
+        """The reference's validation pass (train.py:21-52 with eval=True) over an iterable of device batches or a DeviceFeeder: the
+        per-token averages ``out``, ``temporal_ae``, ``spatial_ae`` (and ``cap_ae`` where that head exists) -- sums of un-normalised
+        terms over summed token counts, as run_epoch returns them -- plus ``tokens``, ``qtokens`` and ``batches``.  The sums are kept on
+        the device by every step's tail launch and read once, here.  Several ranks: each evaluates its own shard, the totals are
+        summed with one all-reduce, and every rank returns the same token-weighted global averages.  A model without the temporal or
+        spatial head reports 0.0 for it, as run_epoch does (SimpleLossCompute.__call__ puts a zero there, optimize.py:92-94)."""
+        names = self._term_names()
+        with self._evaluating():
+            self._eval_totals.zero_()
+            self._eval_counts.zero_()
+            for batch in batches:
+                self._eval_open(batch)
+            packed = torch.cat([self._eval_totals, self._eval_counts.to(torch.float64)])      # (counts: exact in double below 2^53)
+            if self.world > 1:
+                dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=self.pg)
+            host = packed.cpu().tolist()
+        tot = dict(zip(names, host[:len(names)]))
+        tokens, qtokens, nb = (int(round(x)) for x in host[EVAL_TERMS_MAX:EVAL_TERMS_MAX + EVAL_COUNTS])
+        if tokens <= 0 or qtokens <= 0:
+            raise ValueError("bist_amd.Trainer.evaluate: no tokens to average over (an empty validation set?)")
+        out = {"out": tot["out"] / tokens, "temporal_ae": tot.get("temporal_ae", 0.0) / qtokens,
+               "spatial_ae": tot.get("spatial_ae", 0.0) / qtokens}
+        if "cap_ae" in tot:
+            out["cap_ae"] = tot["cap_ae"] / qtokens
+        out.update(tokens=tokens, qtokens=qtokens, batches=nb)
+        return out
+
+    def eval_graph_stats(self) -> Dict[str, int]:
+        """graph_stats() of the validation store: captures, hits, evictions, classes held, the device bytes they hold, the bound."""
+        return dict(self._estats, entries=len(self._eval_entries), bytes=sum(e.bytes for e in self._eval_entries.values()),
+                    max_eval_graphs=self.max_eval_graphs)
 
     def _graph_open(self, batch):
         if self.length_classes is not None:

@@ -657,6 +657,21 @@ typedef struct BistTrainStage {
 int bist_stage_train_batch(const BistTrainStage* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The running totals of a validation pass (train.py:32-37 with eval=True: total_loss += loss, total_tokens += batch.ntokens, ...;
+ * the un-normalised losses are SimpleLossCompute's `term * count`, optimize.py:92-94) as ONE launch (csrc/eval_accum.hip), the tail
+ * of the captured forward-only step of bist_amd/train.py:
+ *   totals[k]             += *terms[k] * *term_counts[k]     k < n_terms    (f32 device scalar, int64 device scalar -> double)
+ *   count_totals[j]       += *counts[j]                      j < n_counts   (int64)
+ *   count_totals[n_counts] += 1                                             (batches)
+ * terms / term_counts / counts are HOST arrays of device pointers (read at the call: a captured launch keeps them).  totals holds
+ * n_terms doubles, count_totals n_counts + 1 int64.  No allocation, no host synchronisation: capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define BIST_EVAL_MAX_TERMS 8
+#define BIST_EVAL_MAX_COUNTS 4
+int bist_eval_accumulate(const void* const* terms, const void* const* term_counts, int32_t n_terms, const void* const* counts,
+                         int32_t n_counts, double* totals, int64_t* count_totals, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Replay of a captured multi-stream hipGraph as ONE LINEAR GRAPH PER STREAM (csrc/graphsplit.hip).
  *
  * The reference runs its step as eager PyTorch launches on one stream (train.py:29-37; there is no graph or executor in the
