@@ -92,6 +92,10 @@ class BistColSum(C.Structure):
     _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("M", C.c_int64), ("N", C.c_int32), ("ldx", C.c_int64)]
 
 
+class BistEmbedBwd(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("dy", C.c_void_p), ("rows", C.c_int64), ("drop", BistDrop)]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); exactly the declarations of include/bist_hip.h
@@ -150,6 +154,13 @@ SIGNATURES = {
     "bist_col_sum_multi": (C.c_int, [C.POINTER(BistColSum), _I32, _I32, _P]),
     "bist_layernorm_param_grad_multi": (C.c_int, [C.POINTER(BistLnGrad), _I32, _I32, _I32, _P]),
     "bist_embed_bwd": (C.c_int, [_P, _P, _P, _I64, _I32, C.POINTER(BistDrop), _I32, _P]),
+    "bist_col_sum_multi_det_workspace": (C.c_int64, [C.POINTER(BistColSum), _I32]),
+    "bist_col_sum_multi_det": (C.c_int, [C.POINTER(BistColSum), _I32, _I32, _P, _I64, _P]),
+    "bist_layernorm_param_grad_multi_det_workspace": (C.c_int64, [C.POINTER(BistLnGrad), _I32, _I32]),
+    "bist_layernorm_param_grad_multi_det": (C.c_int, [C.POINTER(BistLnGrad), _I32, _I32, _I32, _P, _I64, _P]),
+    "bist_scaled_bias_bwd_det_workspace": (C.c_int64, [_I64, _I32, _I32, _I32]),
+    "bist_scaled_bias_bwd_det": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I64, _I32, _P, _I64, _P]),
+    "bist_embed_bwd_multi_det": (C.c_int, [C.POINTER(BistEmbedBwd), _I32, _P, _I64, _I32, _I32, _P]),
     "bist_fuse_modalities_bwd": (C.c_int, [_P, C.POINTER(C.c_void_p), _P, _P, C.POINTER(C.c_void_p), _I64, _I32, _I32, _I32, _P]),
     "bist_mha_core_bwd": (C.c_int, [_P] * 9 + [_I32] * 5 + [_I64] * 16 + [_F, C.POINTER(BistDrop), _I32, _P]),
     "bist_st_stage1_pv_bwd": (C.c_int, [_P] * 5 + [_I32, _P] + [_I32] * 6 + [_I64, _I64, _I32, C.POINTER(BistDrop), _I32, _P]),

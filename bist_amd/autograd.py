@@ -253,7 +253,7 @@ def _linear_grads(x2, w, dz, alpha, w_dst, b_dst, bias_dtype, need_dx, need_dw, 
         if b_dst is not None and ops.COLSUM_QUEUE is not None:
             ops.COLSUM_QUEUE.append((dz, acc, M, N))     # the trainer sums all bias gradients in a few batched launches
         else:
-            check(lib.bist_col_sum_acc(dz.data_ptr(), acc.data_ptr(), M, N, N, dtype_code(dz.dtype), _stream()), "bist_col_sum_acc")
+            ops.col_sum_acc(dz, acc, M, N)
         db = None if b_dst is not None else _to_dtype_from_f32(acc, bias_dtype)
     return dx, dw, db
 
@@ -407,7 +407,7 @@ class HeadUnfoldFn(Function):
         if bdt is None:                      # no bias here: it is applied by ScaledBiasFn (attention dropout)
             return dpy, dwv, None, None
         acc = ctx.b_dst if ctx.b_dst is not None else _f32_zeros((d,), do)
-        check(lib.bist_col_sum_acc(do.data_ptr(), acc.data_ptr(), M, d, d, dtype_code(do.dtype), _stream()), "bist_col_sum_acc")
+        ops.col_sum_acc(do, acc, M, d)
         return dpy, dwv, (None if ctx.b_dst is not None else _to_dtype_from_f32(acc, bdt)), None
 
 
@@ -491,19 +491,27 @@ def _ln_backward(ctx, dy, dres):
     direct = ctx.a_dst is not None and ctx.b_dst is not None
     da, db = (ctx.a_dst, ctx.b_dst) if direct else (_f32_zeros((d,), x), _f32_zeros((d,), x))
     # trainer: dx only on the critical path; the gain/offset gradients of every LayerNorm are summed in one batched launch
-    defer = (direct and ops.LNGRAD_QUEUE is not None and d * x.element_size() == 1024 and a.data_ptr() % 16 == 0
-             and all(t.data_ptr() % 16 == 0 and (t.stride(0) * t.element_size()) % 16 == 0 for t in (dy2, x2) + ((add2,) if add2 is not None else ())))
+    dx_only = (d * x.element_size() == 1024 and a.data_ptr() % 16 == 0          # the envelope of the kernel that writes dx alone
+               and all(t.data_ptr() % 16 == 0 and (t.stride(0) * t.element_size()) % 16 == 0 for t in (dy2, x2) + ((add2,) if add2 is not None else ())))
+    defer = direct and ops.LNGRAD_QUEUE is not None and dx_only
+    det = ops.DETERMINISTIC
+    # deterministic mode: never the in-line atomics -- the kernel writes dx alone (outside that kernel's envelope the general one adds
+    # its parameter sums into a scratch that nobody reads) and the gain / offset gradients are a slab job, queued or run at once
+    sink = torch.empty((2, d), device=x.device, dtype=torch.float32) if (det and not dx_only) else None
     up = getattr(ctx, "up_drop", None)          # x = drop(z) + res came out of a GEMM with this dropout epilogue
     dz = torch.empty(x2.shape, device=x.device, dtype=x.dtype) if (up is not None and up[2] == d) else None
     zdrop = C.byref(ops.BistDrop(up[0], up[1] & 0xFFFFFFFFFFFFFFFF, _ptr(ops.DROP_CTR))) if dz is not None else None
     check(lib.bist_layernorm_bwd(dy2.data_ptr(), x2.data_ptr(), a.data_ptr(), dx.data_ptr(),
-                                 None if defer else da.data_ptr(), None if defer else db.data_ptr(),
+                                 sink[0].data_ptr() if sink is not None else None if (defer or det) else da.data_ptr(),
+                                 sink[1].data_ptr() if sink is not None else None if (defer or det) else db.data_ptr(),
                                  x2.shape[0], d, dy2.stride(0), x2.stride(0), d, eps,
                                  add2.data_ptr() if add2 is not None else None, add2.stride(0) if add2 is not None else 0,
                                  _ptr(dz), zdrop, dtype_code(x.dtype), _stream()),
           "bist_layernorm_bwd")
-    if defer:
+    if defer or (det and direct and ops.LNGRAD_QUEUE is not None):
         ops.LNGRAD_QUEUE.append((dy2, x2, a, da, db, eps))
+    elif det:
+        ops.lngrad_det([(dy2, x2, a, da, db, eps)])
     gx = dx.view(x.shape)
     if dz is not None:
         gx._bist_dz = (dz, up[0], up[1])        # survives only if autograd hands THIS tensor to the producer's backward
@@ -560,6 +568,15 @@ class EmbedFn(Function):
         shape, dt = ctx.cfg
         dy = dy.contiguous()
         acc = ctx.dst if ctx.dst is not None else _f32_zeros(shape, dy)
+        if ops.DETERMINISTIC:
+            # the passes of the fields run on different streams and share the table: queued, the trainer sums them in queue order on
+            # the stream that closes the backward pass; without a queue (or a table of its own) the owner kernel runs here
+            job = (ids.contiguous(), dy.reshape(-1, shape[1]), ctx.drop, acc)
+            if ctx.dst is not None and ops.EMBED_QUEUE is not None:
+                ops.EMBED_QUEUE.append(job)
+            else:
+                ops.embed_bwd_det([job])
+            return None, (None if ctx.dst is not None else _to_dtype_from_f32(acc, dt)), None, None
         check(lib.bist_embed_bwd(ids.contiguous().data_ptr(), dy.data_ptr(), acc.data_ptr(), ids.numel(), shape[1],
                                  ops.drop_ref(ctx.drop), dtype_code(dy.dtype), _stream()), "bist_embed_bwd")
         return None, (None if ctx.dst is not None else _to_dtype_from_f32(acc, dt)), None, None
@@ -690,7 +707,7 @@ class FuseDynFn(Function):
             if ctx.b_dst is not None and ops.COLSUM_QUEUE is not None:
                 ops.COLSUM_QUEUE.append((dscore, acc, M, n))
             else:
-                check(lib.bist_col_sum_acc(dscore.data_ptr(), acc.data_ptr(), M, n, n, dtype_code(dscore.dtype), _stream()), "bist_col_sum_acc")
+                ops.col_sum_acc(dscore, acc, M, n)
             db = None if ctx.b_dst is not None else _to_dtype_from_f32(acc, bdt)
         return (dW, db, None, *grads)
 
@@ -1061,8 +1078,7 @@ class ScaledBiasFn(Function):
         dy2 = dy.reshape(-1, d).contiguous()
         ds = torch.empty(s.shape, device=s.device, dtype=torch.float32)
         acc = ctx.b_dst if ctx.b_dst is not None else _f32_zeros((d,), dy2)
-        check(lib.bist_scaled_bias_bwd(dy2.data_ptr(), s.data_ptr(), bias.data_ptr(), ds.data_ptr(), acc.data_ptr(), dy2.shape[0], h,
-                                       d // h, dtype_code(dy2.dtype), _stream()), "bist_scaled_bias_bwd")
+        ops.scaled_bias_bwd(dy2, s, bias, ds, acc, h)
         return dy, ds, (None if ctx.b_dst is not None else _to_dtype_from_f32(acc, bias.dtype)), None
 
 

@@ -14,7 +14,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import ACT_NONE, ACT_RELU, BF16, F32, BistColSum, BistDrop, BistGemm, BistLnBwdSet, BistLnGrad, BistLnSet, check, lib
+from ._lib import ACT_NONE, ACT_RELU, BF16, F32, BistColSum, BistDrop, BistEmbedBwd, BistGemm, BistLnBwdSet, BistLnGrad, BistLnSet, check, lib
 
 Tensor = torch.Tensor
 
@@ -107,9 +107,137 @@ def _workspace(device) -> Tensor:
     return ws
 
 
+# Deterministic reductions (Trainer(deterministic=True)): while set, every reduction over rows that adds into an
+# fp32 accumulator -- bias, LayerNorm gain / offset, stage-2 value bias, embedding -- runs the slab / owner kernels of det_reduce.hip
+# instead of the float atomics of backward.hip.
+DETERMINISTIC = False
+_DET_WS = {}
+DET_WORKSPACE_BYTES = 16 << 20
+_SPLIT64 = 4              # BIST_GEMM_SPLIT64 (include/bist_hip.h): split-K combined inside the launch by whichever workgroup arrives last
+
+
+def _det_workspace(device) -> Tensor:
+    """Per-(device, stream) fp32 slabs of the deterministic reductions (a partial launch and its combine are neighbours on one stream, so
+    one buffer per stream serves every call on it).  Allocated on first use: the default path never holds it."""
+    key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _DET_WS.get(key)
+    if ws is None:
+        ws = _DET_WS[key] = torch.empty(DET_WORKSPACE_BYTES // 4, device=device, dtype=torch.float32)
+    return ws
+
+
+def _refuse_split64(g: BistGemm) -> None:
+    if DETERMINISTIC and (g.hint & _SPLIT64 or os.environ.get("BIST_GEMM_T64_SPLIT", "0") != "0"):
+        raise RuntimeError("bist_amd: deterministic mode refuses the in-launch split-K combine (hint BIST_GEMM_SPLIT64 / "
+                           "BIST_GEMM_T64_SPLIT): its order of additions follows the order in which workgroups arrive")
+
+
+def _det_runs(jobs, key_of, spans_of, bytes_of, cap: int, max_jobs: int = 1 << 30):
+    """Queue order -> maximal runs of consecutive jobs that may share one call: one key (dtype, width), destinations (byte spans) that do
+    not overlap, slabs that fit the workspace.  Jobs that add into overlapping destinations thereby run in separate calls, in queue order."""
+    i, n = 0, len(jobs)
+    while i < n:
+        key, taken, used, k = key_of(jobs[i]), [], 0, i
+        while k < n and k - i < max_jobs and key_of(jobs[k]) == key:
+            sp, need = spans_of(jobs[k]), bytes_of(jobs[k])
+            if k > i and (used + need > cap or any(lo < thi and tlo < hi for lo, hi in sp for tlo, thi in taken)):
+                break
+            taken += sp
+            used += need
+            k += 1
+        yield key, jobs[i:k]
+        i = k
+
+
+def _col_sum_arr(jobs):
+    arr = (BistColSum * len(jobs))()
+    for i, (dz, acc, M, N) in enumerate(jobs):
+        arr[i].x, arr[i].out, arr[i].M, arr[i].N, arr[i].ldx = dz.data_ptr(), acc.data_ptr(), M, N, N
+    return arr
+
+
+def col_sum_det(jobs) -> None:
+    """(dz, f32 accumulator, M, N) jobs in order through bist_col_sum_multi_det on the current stream."""
+    ws = _det_workspace(jobs[0][0].device)
+    cap = ws.numel() * 4
+    for dt, part in _det_runs(jobs, lambda j: j[0].dtype, lambda j: [(j[1].data_ptr(), j[1].data_ptr() + 4 * j[3])],
+                              lambda j: lib.bist_col_sum_multi_det_workspace(_col_sum_arr([j]), 1), cap):
+        _dev(*[t for j in part for t in j[:2]])
+        check(lib.bist_col_sum_multi_det(_col_sum_arr(part), len(part), dtype_code(dt), ws.data_ptr(), cap, _stream()), "bist_col_sum_multi_det")
+
+
+def col_sum_acc(x: Tensor, acc: Tensor, M: int, N: int) -> None:
+    """acc[n] += sum_m x[m, n] now, on the current stream (a bias gradient outside the trainer's queue)."""
+    if DETERMINISTIC:
+        return col_sum_det([(x, acc, M, N)])
+    check(lib.bist_col_sum_acc(x.data_ptr(), acc.data_ptr(), M, N, N, dtype_code(x.dtype), _stream()), "bist_col_sum_acc")
+
+
+def _ln_grad_arr(jobs):
+    arr = (BistLnGrad * len(jobs))()
+    for i, (dy, x, a, da, db, eps) in enumerate(jobs):
+        arr[i].dy, arr[i].x, arr[i].a, arr[i].da, arr[i].db = dy.data_ptr(), x.data_ptr(), a.data_ptr(), da.data_ptr(), db.data_ptr()
+        arr[i].rows, arr[i].lddy, arr[i].ldx, arr[i].eps = x.shape[0], dy.stride(0), x.stride(0), eps
+    return arr
+
+
+def lngrad_det(jobs) -> None:
+    """(dy, x, gain, da, db, eps) jobs in order through bist_layernorm_param_grad_multi_det on the current stream."""
+    ws = _det_workspace(jobs[0][0].device)
+    cap = ws.numel() * 4
+
+    def spans(j):
+        d = j[1].shape[1]
+        return [(j[3].data_ptr(), j[3].data_ptr() + 4 * d), (j[4].data_ptr(), j[4].data_ptr() + 4 * d)]
+    for (dt, d), part in _det_runs(jobs, lambda j: (j[0].dtype, j[1].shape[1]), spans,
+                                   lambda j: lib.bist_layernorm_param_grad_multi_det_workspace(_ln_grad_arr([j]), 1, j[1].shape[1]), cap):
+        _dev(*[t for j in part for t in j[:5]])
+        check(lib.bist_layernorm_param_grad_multi_det(_ln_grad_arr(part), len(part), d, dtype_code(dt), ws.data_ptr(), cap, _stream()),
+              "bist_layernorm_param_grad_multi_det")
+
+
+def scaled_bias_bwd(dy2: Tensor, s: Tensor, bias: Tensor, ds: Tensor, acc: Tensor, h: int) -> None:
+    """ds and acc += dbias of scaled_bias (bist_scaled_bias_bwd; its deterministic form while DETERMINISTIC is set)."""
+    M, d = dy2.shape
+    if DETERMINISTIC:
+        ws = _det_workspace(dy2.device)
+        check(lib.bist_scaled_bias_bwd_det(dy2.data_ptr(), s.data_ptr(), bias.data_ptr(), ds.data_ptr(), acc.data_ptr(), M, h, d // h, 1, 0, 0,
+                                           dtype_code(dy2.dtype), ws.data_ptr(), ws.numel() * 4, _stream()), "bist_scaled_bias_bwd_det")
+        return
+    check(lib.bist_scaled_bias_bwd(dy2.data_ptr(), s.data_ptr(), bias.data_ptr(), ds.data_ptr(), acc.data_ptr(), M, h,
+                                   d // h, dtype_code(dy2.dtype), _stream()), "bist_scaled_bias_bwd")
+
+
+EMBED_QUEUE = None        # trainer, deterministic mode: list of (ids, dy, drop, f32 table accumulator) embedding-gradient jobs, see embed_flush()
+
+
+def embed_bwd_det(jobs) -> None:
+    """(ids int64 contiguous, dy contiguous [rows, d], (p, seed) or None, f32 accumulator [V, d]) jobs in order through
+    bist_embed_bwd_multi_det on the current stream: consecutive jobs over one table share a launch (up to 16)."""
+    for (ptr, dt, d), part in _det_runs(jobs, lambda j: (j[3].data_ptr(), j[1].dtype, j[3].shape[1]), lambda j: [], lambda j: 0, 1, max_jobs=16):
+        arr = (BistEmbedBwd * len(part))()
+        for i, (ids, dy, drop, acc) in enumerate(part):
+            _dev(ids, dy, acc)
+            arr[i].ids, arr[i].dy, arr[i].rows = ids.data_ptr(), dy.data_ptr(), ids.numel()
+            on = drop is not None and drop[0] > 0.0
+            arr[i].drop = BistDrop(float(drop[0]) if on else 0.0, (int(drop[1]) & 0xFFFFFFFFFFFFFFFF) if on else 0, _ptr(DROP_CTR) if on else None)
+        acc = part[0][3]
+        check(lib.bist_embed_bwd_multi_det(arr, len(part), acc.data_ptr(), acc.shape[0], d, dtype_code(dt), _stream()), "bist_embed_bwd_multi_det")
+
+
+def embed_flush() -> None:
+    """Run the queued embedding gradients (autograd.EmbedFn, deterministic mode) in queue order on the current stream."""
+    q = EMBED_QUEUE
+    if not q:
+        return
+    embed_bwd_det(q)
+    q.clear()
+
+
 def gemm(a: Tensor, b: Tensor, c: Tensor, **kw) -> Tensor:
     """C = epilogue(alpha * A.B^T) with explicit element strides (see include/bist_hip.h)."""
     g = gemm_desc(a, b, c, **kw)
+    _refuse_split64(g)
     if GEMM_TIMING is not None and (GEMM_TIMING_SHAPE is None or GEMM_TIMING_SHAPE == (g.M, g.N, g.K)):
         # bench.py: HIP events around the launch, on the launch stream.  An eager pass is host-bound (~10 us of Python per
         # launch), so the device would reach e0 long before the kernel is even submitted and the interval would include
@@ -132,6 +260,8 @@ LEAF_MASK = 0             # which leaves go there (bist_amd/train.py: LEAF_MASK)
 def gemm_pair(ga: BistGemm, gb: BistGemm) -> None:
     """Two independent products (descriptors from gemm_desc) in one call; one launch when they are the small dX / dW
     pair of a linear layer's backward (bist_gemm_pair)."""
+    _refuse_split64(ga)
+    _refuse_split64(gb)
     check(lib.bist_gemm_pair(C.byref(ga), C.byref(gb), _stream()), "bist_gemm_pair")
 
 
@@ -143,6 +273,10 @@ def col_sum_flush() -> None:
     global COLSUM_QUEUE
     q = COLSUM_QUEUE
     if not q:
+        return
+    if DETERMINISTIC:
+        col_sum_det(q)
+        q.clear()
         return
     by_dtype = {}
     for dz, acc, M, N in q:
@@ -162,6 +296,10 @@ def lngrad_flush() -> None:
     """Sum the queued LayerNorm gain/offset gradients (autograd._ln_backward) in batched launches."""
     q = LNGRAD_QUEUE
     if not q:
+        return
+    if DETERMINISTIC:
+        lngrad_det(q)
+        q.clear()
         return
     groups = {}
     for job in q:

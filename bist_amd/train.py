@@ -112,8 +112,14 @@ class Trainer:
                  warmup: int = 4000, factor: float = 1.0, smoothing: float = 0.1, pad: int = 1,
                  betas=(0.9, 0.98), eps: float = 1e-9, process_group=None, use_graph: bool = False,
                  deferred_adam: Optional[bool] = None, length_classes=None, max_graphs: int = MAX_GRAPHS,
-                 max_eval_graphs: int = MAX_EVAL_GRAPHS):
+                 max_eval_graphs: int = MAX_EVAL_GRAPHS, deterministic: bool = False):
         self.model, self.args = model, args
+        # Bit-reproducible steps: every pass of this trainer -- eager, capture warm-up, capture -- runs with
+        # ops.DETERMINISTIC set, i.e. with the slab / owner reductions of det_reduce.hip in place of the float atomics of backward.hip.
+        self.deterministic = bool(deterministic)
+        if self.deterministic and os.environ.get("BIST_GEMM_T64_SPLIT", "0") != "0":
+            raise ValueError("Trainer(deterministic=True) refuses BIST_GEMM_T64_SPLIT: the in-launch split-K combine adds in the order "
+                             "in which workgroups arrive")
         self.use_graph = use_graph
         self._graph = self._graph2 = self._graph_key = self._static_batch = self._static_terms = None
         self._split = self._split2 = None
@@ -319,6 +325,18 @@ class Trainer:
     def rate(self, step: Optional[int] = None) -> float:
         return parallel.noam_rate(self._step if step is None else step, self.args.d_model, self.factor, self.warmup)
 
+    @contextlib.contextmanager
+    def _det_scope(self):
+        """ops.DETERMINISTIC around a pass of a deterministic trainer (nests; any other trainer leaves the flag as it finds it)."""
+        if not self.deterministic:
+            yield
+            return
+        prev, ops.DETERMINISTIC = ops.DETERMINISTIC, True
+        try:
+            yield
+        finally:
+            ops.DETERMINISTIC = prev
+
     def forward_loss(self, batch):
         ft = self.model.forward(batch)
         terms, logp = self.loss_compute.terms(ft, batch)
@@ -487,6 +505,7 @@ class Trainer:
             after_forward()
         ops.COLSUM_QUEUE = []                 # bias gradients: queued by LinearFn.backward, summed in a few launches by _backward_close
         ops.LNGRAD_QUEUE = []                 # LayerNorm gain/offset gradients: likewise
+        ops.EMBED_QUEUE = [] if self.deterministic else None      # deterministic: the embedding passes of all fields, summed in queue order by _backward_close
         wg = self._wgrad_stream if (self.wgrad_side_stream and loss.is_cuda) else None
         ops.WGRAD_STREAM = wg                 # weight-gradient GEMMs: off the critical path, on their own stream
         # the leaves of the backward pass (frame-grid weight / video gradients) on a chain of their own: only when the step is replayed by
@@ -510,7 +529,7 @@ class Trainer:
                     p._grad_view.add_(p.grad)
                     p.grad = None
         except BaseException:
-            ops.COLSUM_QUEUE = ops.LNGRAD_QUEUE = None
+            ops.COLSUM_QUEUE = ops.LNGRAD_QUEUE = ops.EMBED_QUEUE = None
             raise
         finally:
             self._early_keep.clear()
@@ -525,9 +544,11 @@ class Trainer:
         try:
             ops.col_sum_flush()
             ops.lngrad_flush()
+            ops.embed_flush()
         finally:
             ops.COLSUM_QUEUE = None
             ops.LNGRAD_QUEUE = None
+            ops.EMBED_QUEUE = None
         check(lib.bist_add_f32_into(self.acc32.data_ptr(), self.flat_grad.data_ptr(), self.n32, dtype_code(self.compute_dtype),
                                     _stream()), "bist_add_f32_into")
 
@@ -535,6 +556,10 @@ class Trainer:
         """forward + backward; leaves the complete gradient in ``flat_grad``.  optimizer=True (single rank) also applies
         Adam with the scalars in ``self.hyper``: the big matrices on a side stream BESIDE the closing reductions, the
         prefix of biases / LayerNorm parameters after them."""
+        with self._det_scope():
+            return self._backward(batch, optimizer)
+
+    def _backward(self, batch, optimizer: bool):
         if optimizer and self.deferred and self.flat_grad.is_cuda:
             return self._backward_deferred(batch)
         if optimizer:
@@ -928,6 +953,10 @@ class Trainer:
 
     def step(self, batch) -> Dict[str, torch.Tensor]:
         """One optimiser step; returns the (detached, device-side) loss terms."""
+        with self._det_scope():
+            return self._step_once(batch)
+
+    def _step_once(self, batch) -> Dict[str, torch.Tensor]:
         self._step += 1
         self.drop_ctr.fill_(self._step)
         ops.WEIGHTS_EPOCH += 1               # the parameters change behind autograd's back: derived operands (packed weights) are stale

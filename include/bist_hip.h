@@ -499,6 +499,43 @@ int bist_embed_bwd(const int64_t* ids, const void* dy, float* dlut, int64_t rows
                    int32_t dtype, void* stream);
 int bist_fuse_modalities_bwd(const void* score, const void* const* xs, const void* dout, void* dscore, void* const* dxs,
                              int64_t rows, int32_t n, int32_t d, int32_t dtype, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Deterministic forms of the four row reductions above (det_reduce.hip): the same sums without float
+ * atomics, for bit-reproducible training steps.  Same inputs give the same bits
+ * whatever the order in which workgroups retire, and the result of one job does not depend on which
+ * other jobs share its call.  A (job, row chunk) writes its fp32 partial sums to a slab of `workspace`
+ * (caller-provided, 4-byte aligned; the library never allocates); a second launch on the same stream
+ * sums a job's slabs in chunk order and does one plain `out += total` per element.  The chunking is a
+ * function of the job's own shape.  Two jobs of one call must not overlap in their destinations: the
+ * caller issues such jobs as separate calls, in order.  The *_workspace helpers return the bytes a call
+ * needs (-1: bad arguments); a smaller workspace is refused with BIST_EINVAL before anything is launched.
+ * ------------------------------------------------------------------------------------------ */
+/* bist_col_sum_multi: the bias gradients of nn.Linear (modules.py:76-77,106-109; mtn.py:111; generator.py:18,81) under
+ * loss.backward() (optimize.py:85).  Chunks of max(16, ceil(M / 128)) rows: slabs of ceil(M / chunk) * N floats per job.          */
+int64_t bist_col_sum_multi_det_workspace(const BistColSum* jobs, int32_t njobs);
+int bist_col_sum_multi_det(const BistColSum* jobs, int32_t njobs, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                           void* stream);
+/* bist_layernorm_param_grad_multi: the gradients of a_2 / b_2 of LayerNorm (modules.py:24-31), any d <= 2048 and any alignment
+ * (the job's `a` is not read).  One wave per max(4, ceil(rows / 512)) rows: slabs of ceil(rows / that) * 2 * d floats per job.     */
+int64_t bist_layernorm_param_grad_multi_det_workspace(const BistLnGrad* jobs, int32_t njobs, int32_t d);
+int bist_layernorm_param_grad_multi_det(const BistLnGrad* jobs, int32_t njobs, int32_t d, int32_t dtype, void* workspace,
+                                        int64_t workspace_bytes, void* stream);
+/* bist_scaled_bias_bwd_z: the gradient of the stage-2 value bias under attention dropout (modules.py:63, encoder.py:125-134,152-165).
+ * ds is what bist_scaled_bias_bwd_z writes, bit for bit; dbias[z] += the slabs of set z's row blocks in block order
+ * (blocks of 4 rows, fewer when M / nsets is not a multiple of 4: ceil(M / that) * h * dk floats).                                */
+int64_t bist_scaled_bias_bwd_det_workspace(int64_t M, int32_t h, int32_t dk, int32_t nsets);
+int bist_scaled_bias_bwd_det(const void* dy, const float* s, const void* bias, float* ds, float* dbias, int64_t M, int32_t h,
+                             int32_t dk, int32_t nsets, int64_t bias_zs, int64_t dbias_zs, int32_t dtype, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+/* bist_embed_bwd: the gradient of the shared nn.Embedding (modules.py:118-123) for up to 16 embedding passes over ONE table in one
+ * launch.  Rows are numbered globally in job order; the first row that carries an id owns it, sums dy * sqrt(d) (times the job's
+ * regenerated dropout mask, mask index = row * d + col within the job; drop.p == 0: off) over every row with that id in ascending
+ * global row order, and adds the total to dlut[id, :] once.  Ids outside [0, lut_rows) are skipped.  No workspace.                */
+typedef struct BistEmbedBwd {
+  const int64_t* ids; const void* dy; int64_t rows; BistDrop drop;
+} BistEmbedBwd;
+int bist_embed_bwd_multi_det(const BistEmbedBwd* jobs, int32_t njobs, float* dlut, int64_t lut_rows, int32_t d, int32_t dtype,
+                             void* stream);
 /* dQ/dK/dV of bist_mha_core_fwd; dO and/or dP_ext (gradient w.r.t. the returned probabilities,
  * f32 [N,h,Lq,Lk]) may be NULL (not both).  Gradients are written with their own strides so they
  * can land in column slices of a packed projection gradient.                                     */
