@@ -154,6 +154,10 @@ SIGNATURES = {
     "bist_col_sum_multi": (C.c_int, [C.POINTER(BistColSum), _I32, _I32, _P]),
     "bist_layernorm_param_grad_multi": (C.c_int, [C.POINTER(BistLnGrad), _I32, _I32, _I32, _P]),
     "bist_embed_bwd": (C.c_int, [_P, _P, _P, _I64, _I32, C.POINTER(BistDrop), _I32, _P]),
+    "bist_col_sum_multi_ws_workspace": (C.c_int64, [C.POINTER(BistColSum), _I32]),
+    "bist_col_sum_multi_ws": (C.c_int, [C.POINTER(BistColSum), _I32, _I32, _P, _I64, _P]),
+    "bist_layernorm_param_grad_multi_ws_workspace": (C.c_int64, [C.POINTER(BistLnGrad), _I32, _I32]),
+    "bist_layernorm_param_grad_multi_ws": (C.c_int, [C.POINTER(BistLnGrad), _I32, _I32, _I32, _P, _I64, _P]),
     "bist_col_sum_multi_det_workspace": (C.c_int64, [C.POINTER(BistColSum), _I32]),
     "bist_col_sum_multi_det": (C.c_int, [C.POINTER(BistColSum), _I32, _I32, _P, _I64, _P]),
     "bist_layernorm_param_grad_multi_det_workspace": (C.c_int64, [C.POINTER(BistLnGrad), _I32, _I32]),

@@ -267,6 +267,51 @@ def gemm_pair(ga: BistGemm, gb: BistGemm) -> None:
 
 COLSUM_QUEUE = None       # trainer: list of (dz, acc32 view, M, N) bias-gradient jobs, flushed by col_sum_flush()
 
+# Slab reductions (reduce_slab.hip): while a workspace is registered, col_sum_flush() / lngrad_flush() sum through per-chunk slabs with
+# one atomic per destination element per job instead of one per element per workgroup.  The owner (the trainer) allocates the workspace
+# with reduce_workspace() before any capture and registers the one that belongs to the stream a flush runs on: flushes that share a
+# workspace must be ordered on one stream.
+# Which flushes take the slab kernels: "ln" (default: the LayerNorm jobs -- the column sums measured slower through slabs than through
+# their atomics), "all" (BIST_REDUCE_SLABS=1: the column sums too), "0" (neither: the kernels of backward.hip).
+REDUCE_SLABS = {"0": "0", "1": "all", "all": "all"}.get(os.environ.get("BIST_REDUCE_SLABS", "ln"), "ln")      # tuning aid
+REDUCE_WS = None          # the registered workspace (fp32 tensor from reduce_workspace) or None
+# Size of a workspace.  What a flush needs follows the ROWS of its jobs (4 KiB of slab per 16 rows of a LayerNorm job, at most 128 chunks
+# = 512 KiB per job), so it changes with the batch and its length class, which the trainer does not know when it has to allocate (before
+# the first capture); the number of jobs per flush is the model's.  The B = 16 step of bench.py needs 10.2 MB for all its LayerNorm jobs together
+# (118 of 320 rows, one of 25 088), its four flushes less each; 32 MiB holds that three times over, i.e. every flush of the same model
+# up to B = 48, or 64 jobs of any size.  A
+# flush that needs more runs as several stream-ordered calls (_slab_runs), so the size bounds launches per flush, not correctness.
+REDUCE_WS_BYTES = 32 << 20
+_REDUCE_HEADER = 256      # bytes of counter words at the head of a workspace (include/bist_hip.h)
+
+
+def reduce_workspace(device, nbytes: Optional[int] = None) -> Tensor:
+    """A slab workspace for the flushes of ONE stream: its counter words start as zeros (and every call returns them to zero)."""
+    ws = torch.empty((REDUCE_WS_BYTES if nbytes is None else nbytes) // 4, device=device, dtype=torch.float32)
+    ws[:_REDUCE_HEADER // 4].zero_()
+    return ws
+
+
+def _slab_runs(jobs, need_of, cap: int):
+    """`jobs` as (fits, run) pairs: runs of consecutive jobs whose slabs fit a workspace of `cap` bytes together (one run in the usual
+    case); a job whose slabs alone exceed the workspace is a run of its own with fits = False and takes the atomics entry."""
+    if need_of(jobs) <= cap:
+        yield True, jobs
+        return
+    run, used = [], _REDUCE_HEADER
+    for j in jobs:
+        need = need_of([j]) - _REDUCE_HEADER
+        if run and (used + need > cap or _REDUCE_HEADER + need > cap):
+            yield True, run
+            run, used = [], _REDUCE_HEADER
+        if _REDUCE_HEADER + need > cap:
+            yield False, [j]
+            continue
+        run.append(j)
+        used += need
+    if run:
+        yield True, run
+
 
 def col_sum_flush() -> None:
     """Run every queued bias gradient (autograd.LinearFn) in batched launches on the current stream."""
@@ -278,14 +323,20 @@ def col_sum_flush() -> None:
         col_sum_det(q)
         q.clear()
         return
+    ws = REDUCE_WS if REDUCE_SLABS == "all" else None
     by_dtype = {}
     for dz, acc, M, N in q:
         by_dtype.setdefault(dz.dtype, []).append((dz, acc, M, N))
     for dt, jobs in by_dtype.items():
-        arr = (BistColSum * len(jobs))()
-        for i, (dz, acc, M, N) in enumerate(jobs):
-            arr[i].x, arr[i].out, arr[i].M, arr[i].N, arr[i].ldx = dz.data_ptr(), acc.data_ptr(), M, N, N
-        check(lib.bist_col_sum_multi(arr, len(jobs), dtype_code(dt), _stream()), "bist_col_sum_multi")
+        if ws is not None:
+            cap = ws.numel() * 4
+            for fits, part in _slab_runs(jobs, lambda js: lib.bist_col_sum_multi_ws_workspace(_col_sum_arr(js), len(js)), cap):
+                if fits:
+                    check(lib.bist_col_sum_multi_ws(_col_sum_arr(part), len(part), dtype_code(dt), ws.data_ptr(), cap, _stream()), "bist_col_sum_multi_ws")
+                else:
+                    check(lib.bist_col_sum_multi(_col_sum_arr(part), len(part), dtype_code(dt), _stream()), "bist_col_sum_multi")
+            continue
+        check(lib.bist_col_sum_multi(_col_sum_arr(jobs), len(jobs), dtype_code(dt), _stream()), "bist_col_sum_multi")
     q.clear()
 
 
@@ -301,15 +352,22 @@ def lngrad_flush() -> None:
         lngrad_det(q)
         q.clear()
         return
+    ws = REDUCE_WS if REDUCE_SLABS != "0" else None
     groups = {}
     for job in q:
         groups.setdefault((job[0].dtype, job[1].shape[1]), []).append(job)
     for (dt, d), jobs in groups.items():
-        arr = (BistLnGrad * len(jobs))()
-        for i, (dy, x, a, da, db, eps) in enumerate(jobs):
-            arr[i].dy, arr[i].x, arr[i].a, arr[i].da, arr[i].db = dy.data_ptr(), x.data_ptr(), a.data_ptr(), da.data_ptr(), db.data_ptr()
-            arr[i].rows, arr[i].lddy, arr[i].ldx, arr[i].eps = x.shape[0], dy.stride(0), x.stride(0), eps
-        check(lib.bist_layernorm_param_grad_multi(arr, len(jobs), d, dtype_code(dt), _stream()), "bist_layernorm_param_grad_multi")
+        if ws is not None:
+            cap = ws.numel() * 4
+            # (both entries take rows of 1 KiB, 16-byte aligned, only: autograd._ln_backward defers no other job to this queue)
+            for fits, part in _slab_runs(jobs, lambda js: lib.bist_layernorm_param_grad_multi_ws_workspace(_ln_grad_arr(js), len(js), d), cap):
+                if fits:
+                    check(lib.bist_layernorm_param_grad_multi_ws(_ln_grad_arr(part), len(part), d, dtype_code(dt), ws.data_ptr(), cap, _stream()),
+                          "bist_layernorm_param_grad_multi_ws")
+                else:
+                    check(lib.bist_layernorm_param_grad_multi(_ln_grad_arr(part), len(part), d, dtype_code(dt), _stream()), "bist_layernorm_param_grad_multi")
+            continue
+        check(lib.bist_layernorm_param_grad_multi(_ln_grad_arr(jobs), len(jobs), d, dtype_code(dt), _stream()), "bist_layernorm_param_grad_multi")
     q.clear()
 
 

@@ -261,6 +261,13 @@ class Trainer:
         self.acc32 = torch.zeros(self.n32, device=dev, dtype=torch.float32)
         self.m = torch.zeros(n, device=dev, dtype=torch.float32)
         self.v = torch.zeros(n, device=dev, dtype=torch.float32)
+        # slab workspaces of the deferred bias / LayerNorm-parameter reductions (ops.reduce_workspace, reduce_slab.hip), allocated here --
+        # before any capture, so a replayed step finds them where it recorded them.  One per stream that flushes: the caption chain's
+        # early flushes (_flush_on_caption_chain) and the closing flush on the step's own stream (_backward_close) may run side by side.
+        # A flush whose slabs exceed a workspace is split into calls that fit, in stream order.
+        slabs = ops.REDUCE_SLABS != "0" and dev.type == "cuda" and not self.deterministic
+        self._reduce_ws_chain = ops.reduce_workspace(dev) if slabs else None
+        self._reduce_ws_close = ops.reduce_workspace(dev) if slabs else None
         # {lr, 1 - beta1^t, 1 - beta2^t, grad_scale} of the current step, derived ON THE DEVICE from the step counter (drop_ctr) by
         # bist_noam_hyper at the head of the step: no host buffer that a later step could rewrite while this one is still queued
         self.hyper = torch.zeros(8, device=dev, dtype=torch.float32)
@@ -423,8 +430,12 @@ class Trainer:
         with torch.cuda.stream(cap):
             self._early_keep.extend(ops.COLSUM_QUEUE or [])
             self._early_keep.extend(ops.LNGRAD_QUEUE or [])
-            ops.col_sum_flush()
-            ops.lngrad_flush()
+            ops.REDUCE_WS = self._reduce_ws_chain
+            try:
+                ops.col_sum_flush()
+                ops.lngrad_flush()
+            finally:
+                ops.REDUCE_WS = None
 
     def _bucket_ready(self, cut: int) -> None:
         """Backward-pass callback of the layer loop's mark `cut` (autograd thread): every launch of the backward pass of layers >= cut
@@ -541,11 +552,13 @@ class Trainer:
 
     def _backward_close(self) -> None:
         """The deferred bias / LayerNorm-parameter reductions and the fold of the fp32 prefix into the gradient buffer."""
+        ops.REDUCE_WS = self._reduce_ws_close
         try:
             ops.col_sum_flush()
             ops.lngrad_flush()
             ops.embed_flush()
         finally:
+            ops.REDUCE_WS = None
             ops.COLSUM_QUEUE = None
             ops.LNGRAD_QUEUE = None
             ops.EMBED_QUEUE = None

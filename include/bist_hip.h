@@ -500,6 +500,26 @@ int bist_embed_bwd(const int64_t* ids, const void* dy, float* dlut, int64_t rows
 int bist_fuse_modalities_bwd(const void* score, const void* const* xs, const void* dout, void* dscore, void* const* dxs,
                              int64_t rows, int32_t n, int32_t d, int32_t dtype, void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Slab forms of the two batched reductions above (reduce_slab.hip): the same jobs in ONE launch per batch
+ * with one float atomic per destination element per job.  A (job, row chunk) workgroup writes its fp32
+ * partial row to a slab of `workspace` and takes a ticket on the job's counter word; the workgroup that
+ * draws the job's last ticket sums the job's slabs in chunk order, adds the total to the destination
+ * (atomically: jobs of one call MAY share a destination) and returns the counter to zero.  No workgroup
+ * waits for another.  `workspace` (caller-provided, 16-byte aligned): 256 bytes of counter words, which
+ * must be zero before the first call (every call leaves them zero), then the slabs.  Calls that share a
+ * workspace must be ordered on one stream.  The *_workspace helpers return the bytes a call needs
+ * (-1: bad arguments); a smaller workspace is refused with BIST_EINVAL before anything is launched.
+ * ------------------------------------------------------------------------------------------ */
+/* Chunks of max(16, ceil(M / 128)) rows: 256 + 4 * sum over jobs of ceil(M / chunk) * (N rounded up to 4) bytes.                  */
+int64_t bist_col_sum_multi_ws_workspace(const BistColSum* jobs, int32_t njobs);
+int bist_col_sum_multi_ws(const BistColSum* jobs, int32_t njobs, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+/* Rows of 1 KiB (d = 512 bf16 / 256 f32), 16-byte aligned; the job's `a` is not read.  Chunks of 4 * max(4, ceil(rows / 512)) rows
+ * (one workgroup, four waves): 256 + 4 * sum over jobs of ceil(rows / chunk) * 2 * d bytes.                                       */
+int64_t bist_layernorm_param_grad_multi_ws_workspace(const BistLnGrad* jobs, int32_t njobs, int32_t d);
+int bist_layernorm_param_grad_multi_ws(const BistLnGrad* jobs, int32_t njobs, int32_t d, int32_t dtype, void* workspace,
+                                       int64_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
  * Deterministic forms of the four row reductions above (det_reduce.hip): the same sums without float
  * atomics, for bit-reproducible training steps.  Same inputs give the same bits
  * whatever the order in which workgroups retire, and the result of one job does not depend on which
