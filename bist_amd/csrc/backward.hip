@@ -495,11 +495,14 @@ __global__ void add_f32_into_kernel(const float* __restrict__ s, T* __restrict__
 // (torch.optim.Adam semantics, the optimiser the reference wraps in NoamOpt, train.py:129-130)
 // hyper (nullable, device): {lr, 1 - beta1^t, 1 - beta2^t, grad_scale} of THIS step -- lets the launch live inside a captured
 // hipGraph, whose kernel arguments are frozen at capture time
-// one element of torch.optim.Adam (both kernels below call this, so they round alike)
+// one element of torch.optim.Adam (every kernel below calls this, so they round alike).  The fused multiply-adds are spelled out: they
+// are the contractions the compiler chose for adam_kernel, adam4_kernel and adam_apply4_kernel from the plain expressions
+// (m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g; p = p - lr (..)), but which product of a sum of two it fuses depends on the code
+// around the call -- in adam_accum_kernel it picked fma(1 - b1, g, b1 m) -- and two kernels then differ in the last bit
 __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, float lr, float b1, float b2, float eps, float bc1, float bc2) {
-  m = b1 * m + (1.f - b1) * g;
-  v = b2 * v + (1.f - b2) * g * g;
-  p = p - lr * ((m / bc1) / (sqrtf(v / bc2) + eps));
+  m = __builtin_fmaf(b1, m, (1.f - b1) * g);
+  v = __builtin_fmaf(b2, v, (1.f - b2) * g * g);
+  p = __builtin_fmaf(-lr, (m / bc1) / (sqrtf(v / bc2) + eps), p);
 }
 template <typename TG, typename TW>
 __global__ void adam_kernel(float* __restrict__ p, const TG* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -536,6 +539,81 @@ __global__ __launch_bounds__(256) void adam4_kernel(float* __restrict__ p, const
   float pv[4] = {pm.x, pm.y, pm.z, pm.w}, mv[4] = {mm.x, mm.y, mm.z, mm.w}, vv[4] = {vm.x, vm.y, vm.z, vm.w};
 #pragma unroll
   for (int e = 0; e < 4; ++e) adam_elem(pv[e], mv[e], vv[e], gi[e] * gscale, lr, b1, b2, eps, bc1, bc2);
+  reinterpret_cast<float4*>(m)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
+  reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
+  reinterpret_cast<float4*>(p)[i] = make_float4(pv[0], pv[1], pv[2], pv[3]);
+  if (work) {
+    if constexpr (sizeof(TW) == 2) {
+      typedef __attribute__((ext_vector_type(2))) float f32x2_;
+      typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
+      const bf16x2_ lo = __builtin_convertvector(f32x2_{pv[0], pv[1]}, bf16x2_), hi = __builtin_convertvector(f32x2_{pv[2], pv[3]}, bf16x2_);
+      reinterpret_cast<uint2*>(work)[i] = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
+    } else {
+      reinterpret_cast<float4*>(work)[i] = make_float4(pv[0], pv[1], pv[2], pv[3]);
+    }
+  }
+  }
+}
+
+// One optimiser step over SEVERAL backward passes (the reference takes its update from more clips than one pass holds: run_epoch,
+// train.py:29-37, calls NoamOpt.step, optimize.py:19-26, once per batch, on gradients of terms divided by the batch's token counts,
+// optimize.py:48-50): the tail of every pass of a group is this launch, and the device word phase[0] -- read once per thread, a uniform
+// load -- says which pass it is.  Bit 0 = first pass of the group, bit 1 = last:
+//   s = first ? g : acc + g            (fp32; the first pass never reads acc, so acc needs no memset)
+//   last  : adam_elem on s * grad_scale, work = cast(p); acc is not written
+//   else  : acc = s; p / m / v / work are neither read nor written
+// g is never written.  With phase 3 (a group of one) element for element adam4_kernel / adam_kernel.  A captured launch therefore
+// serves every pass of every group: only the word changes between replays.
+template <typename TG, typename TW>
+__global__ void adam_accum_kernel(float* __restrict__ p, const TG* __restrict__ g, float* __restrict__ acc, float* __restrict__ m,
+                                  float* __restrict__ v, TW* __restrict__ work, long n, float b1, float b2, float eps,
+                                  const float* __restrict__ hyper, const int* __restrict__ phase) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int ph = phase[0];
+  float s = to_f(g[i]);
+  if (!(ph & 1)) s = acc[i] + s;
+  if (!(ph & 2)) { acc[i] = s; return; }
+  const float lr = hyper[0], bc1 = hyper[1], bc2 = hyper[2], gscale = hyper[3];
+  float mi = m[i], vi = v[i], pi = p[i];
+  adam_elem(pi, mi, vi, s * gscale, lr, b1, b2, eps, bc1, bc2);
+  m[i] = mi; v[i] = vi;
+  p[i] = pi;
+  if (work) work[i] = from_f<TW>(pi);
+}
+
+// adam_accum_kernel on 4 elements per thread, grid-stride (the accesses of adam4_kernel, plus 16 bytes of acc): n4 = n / 4
+template <typename TG, typename TW>
+__global__ __launch_bounds__(256) void adam_accum4_kernel(float* __restrict__ p, const TG* __restrict__ g, float* __restrict__ acc,
+                                                          float* __restrict__ m, float* __restrict__ v, TW* __restrict__ work, long n4,
+                                                          float b1, float b2, float eps, const float* __restrict__ hyper,
+                                                          const int* __restrict__ phase) {
+  const int ph = phase[0];
+  const bool first = (ph & 1) != 0, last = (ph & 2) != 0;
+  float lr = 0.f, bc1 = 1.f, bc2 = 1.f, gscale = 1.f;
+  if (last) { lr = hyper[0]; bc1 = hyper[1]; bc2 = hyper[2]; gscale = hyper[3]; }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+  float s[4];
+  if constexpr (sizeof(TG) == 2) {
+    const uint2 q = reinterpret_cast<const uint2*>(g)[i];
+    s[0] = __builtin_bit_cast(float, q.x << 16); s[1] = __builtin_bit_cast(float, q.x & 0xffff0000u);
+    s[2] = __builtin_bit_cast(float, q.y << 16); s[3] = __builtin_bit_cast(float, q.y & 0xffff0000u);
+  } else {
+    const float4 q = reinterpret_cast<const float4*>(g)[i];
+    s[0] = q.x; s[1] = q.y; s[2] = q.z; s[3] = q.w;
+  }
+  if (!first) {
+    const float4 a = reinterpret_cast<const float4*>(acc)[i];
+    s[0] = a.x + s[0]; s[1] = a.y + s[1]; s[2] = a.z + s[2]; s[3] = a.w + s[3];
+  }
+  if (!last) {
+    reinterpret_cast<float4*>(acc)[i] = make_float4(s[0], s[1], s[2], s[3]);
+    continue;
+  }
+  const float4 pm = reinterpret_cast<const float4*>(p)[i], mm = reinterpret_cast<const float4*>(m)[i], vm = reinterpret_cast<const float4*>(v)[i];
+  float pv[4] = {pm.x, pm.y, pm.z, pm.w}, mv[4] = {mm.x, mm.y, mm.z, mm.w}, vv[4] = {vm.x, vm.y, vm.z, vm.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) adam_elem(pv[e], mv[e], vv[e], s[e] * gscale, lr, b1, b2, eps, bc1, bc2);
   reinterpret_cast<float4*>(m)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
   reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
   reinterpret_cast<float4*>(p)[i] = make_float4(pv[0], pv[1], pv[2], pv[3]);
@@ -1057,5 +1135,35 @@ extern "C" int bist_adam_apply_dev(float* p, void* g, float* m, float* v, void* 
   else { bist_set_error("bist_adam_apply_dev: bad dtype combination"); return BIST_EINVAL; }
 #undef ADAM
   BIST_LAUNCH_CHECK("bist_adam_apply_dev");
+  return BIST_OK;
+}
+
+// Adam over a group of backward passes (adam_accum4_kernel above): `phase` is one device int32, bit 0 = first pass of the group, bit 1 =
+// last.  max_blocks as in bist_adam_step_dev_bg.
+extern "C" int bist_adam_accum_dev(float* p, const void* g, float* acc, float* m, float* v, void* work, int64_t n, const float* hyper,
+                                   const int32_t* phase, float beta1, float beta2, float eps, int32_t grad_dtype, int32_t work_dtype,
+                                   int32_t max_blocks, void* stream) {
+  BIST_REQUIRE(p && g && acc && m && v && hyper && phase && n > 0 && max_blocks >= 0, "bist_adam_accum_dev: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  // whole 16-byte groups: four elements per thread
+  const bool vec = n % 4 == 0 && ((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc) % 16 == 0 &&
+                   (uintptr_t)g % (grad_dtype == BIST_BF16 ? 8 : 16) == 0 && (!work || (uintptr_t)work % (work_dtype == BIST_BF16 ? 8 : 16) == 0);
+  unsigned grid = vec ? blocks_for(n / 4, 256) : blocks_for(n, 256);
+  if (max_blocks > 0) {
+    BIST_REQUIRE(vec, "bist_adam_accum_dev: the background form needs whole 16-byte groups (n %% 4 == 0, aligned pointers)");
+    if (grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
+  }
+#define ADAM(TG, TW)                                                                                                                                  \
+  do {                                                                                                                                                \
+    if (vec) hipLaunchKernelGGL((adam_accum4_kernel<TG, TW>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, acc, m, v, (TW*)work, (long)(n / 4), beta1, beta2, eps, hyper, (const int*)phase); \
+    else hipLaunchKernelGGL((adam_accum_kernel<TG, TW>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, acc, m, v, (TW*)work, (long)n, beta1, beta2, eps, hyper, (const int*)phase); \
+  } while (0)
+  if (grad_dtype == BIST_F32 && (work == nullptr || work_dtype == BIST_F32)) ADAM(float, float);
+  else if (grad_dtype == BIST_F32 && work_dtype == BIST_BF16) ADAM(float, bf16_t);
+  else if (grad_dtype == BIST_BF16 && (work == nullptr || work_dtype == BIST_BF16)) ADAM(bf16_t, bf16_t);
+  else if (grad_dtype == BIST_BF16 && work_dtype == BIST_F32) ADAM(bf16_t, float);
+  else { bist_set_error("bist_adam_accum_dev: bad dtype combination"); return BIST_EINVAL; }
+#undef ADAM
+  BIST_LAUNCH_CHECK("bist_adam_accum_dev");
   return BIST_OK;
 }

@@ -112,7 +112,7 @@ class Trainer:
                  warmup: int = 4000, factor: float = 1.0, smoothing: float = 0.1, pad: int = 1,
                  betas=(0.9, 0.98), eps: float = 1e-9, process_group=None, use_graph: bool = False,
                  deferred_adam: Optional[bool] = None, length_classes=None, max_graphs: int = MAX_GRAPHS,
-                 max_eval_graphs: int = MAX_EVAL_GRAPHS, deterministic: bool = False):
+                 max_eval_graphs: int = MAX_EVAL_GRAPHS, deterministic: bool = False, accumulate: bool = False):
         self.model, self.args = model, args
         # Bit-reproducible steps: every pass of this trainer -- eager, capture warm-up, capture -- runs with
         # ops.DETERMINISTIC set, i.e. with the slab / owner reductions of det_reduce.hip in place of the float atomics of backward.hip.
@@ -162,6 +162,21 @@ class Trainer:
             deferred_adam = os.environ.get("BIST_DEFERRED_ADAM", "0") != "0"
         self.deferred = bool(deferred_adam) and self.adam_in_step and use_graph
         self._pending_host = False
+        # One optimiser step over several batches (step_group): every Adam launch of the step becomes
+        # bist_adam_accum_dev, which a device-side phase word turns into "add to the fp32 accumulator" on all passes of a group but the last.
+        self.accumulate = bool(accumulate)
+        if self.accumulate:
+            if self.world > 1 or os.environ.get("BIST_FORCE_EXCHANGE") == "1":
+                raise ValueError("Trainer(accumulate=True) refuses several ranks (and BIST_FORCE_EXCHANGE): the exchange sums the bf16 gradient "
+                                 "buffer of one pass; accumulating across ranks and passes is a separate change")
+            if deferred_adam:
+                raise ValueError("Trainer(accumulate=True) refuses deferred_adam: the deferred update reads the gradient buffer of one pass at "
+                                 "the head of the next")
+            if not self.adam_in_step:
+                raise ValueError("Trainer(accumulate=True) refuses BIST_ADAM_IN_STEP=0: the accumulating launch is the tail of the step itself")
+            if ADAM_CLEARS:
+                raise ValueError("Trainer(accumulate=True) refuses BIST_ADAM_CLEARS=1: the accumulating launch never writes the gradient buffer, "
+                                 "the head of every pass clears it")
 
         params: List[torch.nn.Parameter] = []
         seen = set()
@@ -261,6 +276,15 @@ class Trainer:
         self.acc32 = torch.zeros(self.n32, device=dev, dtype=torch.float32)
         self.m = torch.zeros(n, device=dev, dtype=torch.float32)
         self.v = torch.zeros(n, device=dev, dtype=torch.float32)
+        if self.accumulate:
+            # allocated here, before any capture: the sum of a group's gradients in fp32 (the gradient buffer is in the compute dtype: a
+            # running sum kept there would round the whole sum after every pass), the phase word of bist_adam_accum_dev, and the number of
+            # the optimiser step -- drop_ctr counts PASSES on such a trainer (fresh dropout masks per pass), opt_ctr counts UPDATES (the
+            # Noam rate and the bias corrections, bist_noam_hyper).  The first pass of a group never reads acc: no memset.
+            self.acc = torch.empty(n, device=dev, dtype=torch.float32)
+            self.phase = torch.zeros(1, device=dev, dtype=torch.int32)
+            self.opt_ctr = torch.zeros(1, device=dev, dtype=torch.int64)
+            self._passes = 0
         # slab workspaces of the deferred bias / LayerNorm-parameter reductions (ops.reduce_workspace, reduce_slab.hip), allocated here --
         # before any capture, so a replayed step finds them where it recorded them.  One per stream that flushes: the caption chain's
         # early flushes (_flush_on_caption_chain) and the closing flush on the step's own stream (_backward_close) may run side by side.
@@ -351,11 +375,19 @@ class Trainer:
 
     def _adam_dev(self, lo: int, hi: int, max_blocks: int = 0) -> None:
         """Adam on flat elements [lo, hi) with this step's scalars read from ``self.hyper`` (device): capturable.  max_blocks > 0: as a
-        background launch of that many workgroups (bist_adam_step_dev_bg)."""
+        background launch of that many workgroups (bist_adam_step_dev_bg).  accumulate=True: the same range through bist_adam_accum_dev,
+        which adds the pass's gradient into ``self.acc`` and runs Adam only in the last pass of a group (``self.phase``)."""
         if hi <= lo:
             return
         work = None if self.compute_dtype == torch.float32 else self.flat_param
         gsz = self.flat_grad.element_size()
+        if self.accumulate:
+            check(lib.bist_adam_accum_dev(self.master.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + gsz * lo, self.acc.data_ptr() + 4 * lo,
+                                          self.m.data_ptr() + 4 * lo, self.v.data_ptr() + 4 * lo,
+                                          (work.data_ptr() + work.element_size() * lo) if work is not None else None, hi - lo,
+                                          self.hyper.data_ptr(), self.phase.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                                          dtype_code(self.compute_dtype), dtype_code(self.compute_dtype), max_blocks, _stream()), "bist_adam_accum_dev")
+            return
         check(lib.bist_adam_step_dev_bg(self.master.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + gsz * lo, self.m.data_ptr() + 4 * lo,
                                         self.v.data_ptr() + 4 * lo, (work.data_ptr() + work.element_size() * lo) if work is not None else None,
                                         hi - lo, self.hyper.data_ptr(), self.betas[0], self.betas[1], self.eps,
@@ -576,7 +608,8 @@ class Trainer:
         if optimizer and self.deferred and self.flat_grad.is_cuda:
             return self._backward_deferred(batch)
         if optimizer:
-            check(lib.bist_noam_hyper(self.drop_ctr.data_ptr(), self.hyper.data_ptr(), float(self.args.d_model), float(self.factor),
+            ctr = self.opt_ctr if self.accumulate else self.drop_ctr
+            check(lib.bist_noam_hyper(ctr.data_ptr(), self.hyper.data_ptr(), float(self.args.d_model), float(self.factor),
                                       float(self.warmup), self.betas[0], self.betas[1], 1.0, _stream()), "bist_noam_hyper")
         # one rank, optimiser in the step: Adam clears every gradient it consumes (bist_adam_apply_dev), so a REPLAYED step starts from a
         # clean buffer without a memset of its own (_graph_open clears it when something else left a gradient behind)
@@ -966,8 +999,67 @@ class Trainer:
 
     def step(self, batch) -> Dict[str, torch.Tensor]:
         """One optimiser step; returns the (detached, device-side) loss terms."""
+        if self.accumulate:
+            return self.step_group([batch])
         with self._det_scope():
             return self._step_once(batch)
+
+    def step_group(self, batches) -> Dict[str, torch.Tensor]:
+        """One optimiser step over a list of batches (Trainer(accumulate=True)): the reference's update on their UNION.  Every loss term
+        of every pass is divided by the token counts of the whole group (summed on the device; the mechanism of _globally_normalised:
+        each batch goes on as a shallow copy carrying the totals), the passes' gradients are summed in fp32 (bist_adam_accum_dev) and the
+        last pass ends in Adam on the sum.  Each pass runs as a step does -- the same captured graph serves every pass, only the device
+        words `phase`, `drop_ctr` (the pass count: fresh dropout masks) and `opt_ctr` (the update count: rate and bias corrections)
+        change between replays.  Returns each loss term summed over the passes (device scalars): the per-token term of the union.  No
+        host synchronisation."""
+        if not self.accumulate:
+            raise ValueError("Trainer.step_group needs a trainer built with accumulate=True (its buffers exist before any capture)")
+        batches = list(batches)
+        if not batches:
+            raise ValueError("Trainer.step_group: an empty group is no optimiser step")
+        with self._det_scope():
+            return self._step_group(batches)
+
+    def _step_group(self, batches) -> Dict[str, torch.Tensor]:
+        for b in batches:
+            if hasattr(b, "move_to_cuda") and not b.query.is_cuda and self.flat_param.is_cuda:
+                b.move_to_cuda()
+        if len(batches) > 1:
+            has_n = batches[0].ntokens is not None
+            nt = torch.stack([b.ntokens.reshape(()) for b in batches]).sum() if has_n else None
+            qn = torch.stack([b.qntokens.reshape(()) for b in batches]).sum()
+            b0 = batches[0]                  # (shape and dtype as found: the exact-shape graph is keyed by them; ONE tensor object per count
+            if has_n:                        # for the whole group, so that the replayed step copies it once, not per pass)
+                nt = nt.to(b0.ntokens.dtype).reshape(b0.ntokens.shape)
+            qn = qn.to(b0.qntokens.dtype).reshape(b0.qntokens.shape)
+            passes = []
+            for b in batches:
+                gb = copy.copy(b)
+                if has_n:
+                    gb.ntokens = nt
+                gb.qntokens = qn
+                passes.append(gb)
+        else:
+            passes = batches
+        self._step += 1
+        self.opt_ctr.fill_(self._step)
+        ops.WEIGHTS_EPOCH += 1               # (once per group: the parameters change in its last pass only)
+        total: Dict[str, torch.Tensor] = {}
+        last = len(passes) - 1
+        if last == 0:                        # a group of one: the launches of _step_once, its static outputs returned as they are
+            self._passes += 1
+            self.drop_ctr.fill_(self._passes)
+            self.phase.fill_(3)
+            terms = self._graph_open(passes[0]) if self.use_graph else self.backward(passes[0], optimizer=True)
+            return {k: v.detach() for k, v in terms.items()}
+        for i, gb in enumerate(passes):
+            self._passes += 1
+            self.drop_ctr.fill_(self._passes)
+            self.phase.fill_((1 if i == 0 else 0) | (2 if i == last else 0))
+            terms = self._graph_open(gb) if self.use_graph else self.backward(gb, optimizer=True)
+            for k, v in terms.items():       # (a replayed pass returns its graph's static outputs: added before the next replay rewrites them)
+                total[k] = v.detach().clone() if i == 0 else total[k] + v.detach()
+        return total
 
     def _step_once(self, batch) -> Dict[str, torch.Tensor]:
         self._step += 1

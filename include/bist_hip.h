@@ -663,6 +663,16 @@ int bist_adam_step_dev(float* p, const void* g, float* m, float* v, void* work, 
  * run beside the latency-bound launches of a backward pass without taking the CUs' wave slots from them (n % 4 == 0, aligned pointers). */
 int bist_adam_step_dev_bg(float* p, const void* g, float* m, float* v, void* work, int64_t n, const float* hyper, float beta1,
                           float beta2, float eps, int32_t grad_dtype, int32_t work_dtype, int32_t max_blocks, void* stream);
+/* One optimiser step over a GROUP of backward passes (the reference's update from more clips than one pass holds: run_epoch,
+ * train.py:29-37, steps NoamOpt, optimize.py:19-26, once per batch of per-token terms, optimize.py:48-50).  This launch is the tail of
+ * every pass; phase[0] (device int32, read once per thread) says which: bit 0 = first pass of the group, bit 1 = last.
+ *   s = first ? float(g) : acc + float(g)   (acc: fp32, n elements; the first pass never reads it, so it needs no memset)
+ *   not last: acc = s; p, m, v, work untouched.      last: bist_adam_step_dev on s (times grad_scale), acc untouched.
+ * g is never written.  Phase 3 writes the bits of bist_adam_step_dev_bg.  max_blocks and its alignment contract as there; ranges
+ * that are not whole 16-byte groups take a scalar form (max_blocks == 0 only).  A captured launch serves every pass of a group.   */
+int bist_adam_accum_dev(float* p, const void* g, float* acc, float* m, float* v, void* work, int64_t n, const float* hyper,
+                        const int32_t* phase, float beta1, float beta2, float eps, int32_t grad_dtype, int32_t work_dtype,
+                        int32_t max_blocks, void* stream);
 /* Deferred form: the update of optimiser step t is applied at the HEAD of step t+1, beside its forward pass (the tail of a step is
  * then the backward pass alone).  bist_noam_hyper_pending reads t = pending[0] (device int64; 0 = nothing pending), writes
  * hyper[0..4] = {rate(t), 1 - beta1^t, 1 - beta2^t, grad_scale, apply = (t > 0)} and sets pending[0] = 0; the caller sets
