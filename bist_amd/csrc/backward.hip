@@ -504,10 +504,14 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
   v = __builtin_fmaf(b2, v, (1.f - b2) * g * g);
   p = __builtin_fmaf(-lr, (m / bc1) / (sqrtf(v / bc2) + eps), p);
 }
-template <typename TG, typename TW>
+// GUARD (bist_adam_step_dev_guard, bist_adam_accum_dev_guard; needs hyper): a launch that would run Adam returns at its head when the
+// skip word hyper[5] is set (bist_clip_hyper: the step's gradient norm is not finite) and leaves p / m / v / work as they are.  One
+// uniform load; with hyper[5] == 0 the bits of the unguarded kernel.  GUARD = false is the code every other entry point launches.
+template <typename TG, typename TW, bool GUARD = false>
 __global__ void adam_kernel(float* __restrict__ p, const TG* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             TW* __restrict__ work, long n, float lr, float b1, float b2, float eps, float bc1, float bc2, float gscale,
                             const float* __restrict__ hyper) {
+  if constexpr (GUARD) { if (hyper[5] != 0.f) return; }
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2 = hyper[2]; gscale = hyper[3]; }
@@ -519,9 +523,10 @@ __global__ void adam_kernel(float* __restrict__ p, const TG* __restrict__ g, flo
 }
 
 // adam_kernel on 4 elements per thread (16-byte accesses of p / m / v, 8 or 16 of the gradient and the working copy): n4 = n / 4
-template <typename TG, typename TW>
+template <typename TG, typename TW, bool GUARD = false>
 __global__ __launch_bounds__(256) void adam4_kernel(float* __restrict__ p, const TG* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                     TW* __restrict__ work, long n4, float b1, float b2, float eps, const float* __restrict__ hyper) {
+  if constexpr (GUARD) { if (hyper[5] != 0.f) return; }
   const float lr = hyper[0], bc1 = hyper[1], bc2 = hyper[2], gscale = hyper[3];
   // grid-stride: one pass for the chip-filling launch; the BACKGROUND form (bist_adam_step_dev_bg) runs a few hundred workgroups that
   // leave the CUs' wave slots to the step's small launches
@@ -564,13 +569,14 @@ __global__ __launch_bounds__(256) void adam4_kernel(float* __restrict__ p, const
 //   else  : acc = s; p / m / v / work are neither read nor written
 // g is never written.  With phase 3 (a group of one) element for element adam4_kernel / adam_kernel.  A captured launch therefore
 // serves every pass of every group: only the word changes between replays.
-template <typename TG, typename TW>
+template <typename TG, typename TW, bool GUARD = false>
 __global__ void adam_accum_kernel(float* __restrict__ p, const TG* __restrict__ g, float* __restrict__ acc, float* __restrict__ m,
                                   float* __restrict__ v, TW* __restrict__ work, long n, float b1, float b2, float eps,
                                   const float* __restrict__ hyper, const int* __restrict__ phase) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int ph = phase[0];
+  if constexpr (GUARD) { if ((ph & 2) && hyper[5] != 0.f) return; }      // the last pass only: first and middle passes accumulate as before
   float s = to_f(g[i]);
   if (!(ph & 1)) s = acc[i] + s;
   if (!(ph & 2)) { acc[i] = s; return; }
@@ -583,13 +589,14 @@ __global__ void adam_accum_kernel(float* __restrict__ p, const TG* __restrict__ 
 }
 
 // adam_accum_kernel on 4 elements per thread, grid-stride (the accesses of adam4_kernel, plus 16 bytes of acc): n4 = n / 4
-template <typename TG, typename TW>
+template <typename TG, typename TW, bool GUARD = false>
 __global__ __launch_bounds__(256) void adam_accum4_kernel(float* __restrict__ p, const TG* __restrict__ g, float* __restrict__ acc,
                                                           float* __restrict__ m, float* __restrict__ v, TW* __restrict__ work, long n4,
                                                           float b1, float b2, float eps, const float* __restrict__ hyper,
                                                           const int* __restrict__ phase) {
   const int ph = phase[0];
   const bool first = (ph & 1) != 0, last = (ph & 2) != 0;
+  if constexpr (GUARD) { if (last && hyper[5] != 0.f) return; }
   float lr = 0.f, bc1 = 1.f, bc2 = 1.f, gscale = 1.f;
   if (last) { lr = hyper[0]; bc1 = hyper[1]; bc2 = hyper[2]; gscale = hyper[3]; }
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -1083,31 +1090,44 @@ extern "C" int bist_adam_step_dev(float* p, const void* g, float* m, float* v, v
   return bist_adam_step_dev_bg(p, g, m, v, work, n, hyper, beta1, beta2, eps, grad_dtype, work_dtype, 0, stream);
 }
 // max_blocks > 0: at most that many workgroups walk the range (a background update beside latency-bound launches); 0: one element group per thread
-extern "C" int bist_adam_step_dev_bg(float* p, const void* g, float* m, float* v, void* work, int64_t n, const float* hyper, float beta1,
-                                     float beta2, float eps, int32_t grad_dtype, int32_t work_dtype, int32_t max_blocks, void* stream) {
-  BIST_REQUIRE(p && g && m && v && hyper && n > 0 && max_blocks >= 0, "bist_adam_step_dev: bad argument");
+template <bool GUARD>
+static int adam_step_dev_launch(float* p, const void* g, float* m, float* v, void* work, int64_t n, const float* hyper, float beta1,
+                                float beta2, float eps, int32_t grad_dtype, int32_t work_dtype, int32_t max_blocks, void* stream,
+                                const char* who, const char* who_bg) {
+  BIST_REQUIRE(p && g && m && v && hyper && n > 0 && max_blocks >= 0, "%s: bad argument", who);
   hipStream_t st = (hipStream_t)stream;
   // whole 16-byte groups: four elements per thread
   const bool vec = n % 4 == 0 && ((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) % 16 == 0 && (uintptr_t)g % (grad_dtype == BIST_BF16 ? 8 : 16) == 0 &&
                    (!work || (uintptr_t)work % (work_dtype == BIST_BF16 ? 8 : 16) == 0);
   unsigned grid = vec ? blocks_for(n / 4, 256) : blocks_for(n, 256);
   if (max_blocks > 0) {
-    BIST_REQUIRE(vec, "bist_adam_step_dev_bg: the background form needs whole 16-byte groups (n %% 4 == 0, aligned pointers)");
+    BIST_REQUIRE(vec, "%s: the background form needs whole 16-byte groups (n %% 4 == 0, aligned pointers)", who_bg);
     if (grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
   }
 #define ADAM(TG, TW)                                                                                                                                  \
   do {                                                                                                                                                \
-    if (vec) hipLaunchKernelGGL((adam4_kernel<TG, TW>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, m, v, (TW*)work, (long)(n / 4), beta1, beta2, eps, hyper); \
-    else hipLaunchKernelGGL((adam_kernel<TG, TW>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, m, v, (TW*)work, (long)n, 0.f, beta1, beta2, eps, 1.f, 1.f, 1.f, hyper); \
+    if (vec) hipLaunchKernelGGL((adam4_kernel<TG, TW, GUARD>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, m, v, (TW*)work, (long)(n / 4), beta1, beta2, eps, hyper); \
+    else hipLaunchKernelGGL((adam_kernel<TG, TW, GUARD>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, m, v, (TW*)work, (long)n, 0.f, beta1, beta2, eps, 1.f, 1.f, 1.f, hyper); \
   } while (0)
   if (grad_dtype == BIST_F32 && (work == nullptr || work_dtype == BIST_F32)) ADAM(float, float);
   else if (grad_dtype == BIST_F32 && work_dtype == BIST_BF16) ADAM(float, bf16_t);
   else if (grad_dtype == BIST_BF16 && (work == nullptr || work_dtype == BIST_BF16)) ADAM(bf16_t, bf16_t);
   else if (grad_dtype == BIST_BF16 && work_dtype == BIST_F32) ADAM(bf16_t, float);
-  else { bist_set_error("bist_adam_step_dev: bad dtype combination"); return BIST_EINVAL; }
+  else { bist_set_error("%s: bad dtype combination", who); return BIST_EINVAL; }
 #undef ADAM
-  BIST_LAUNCH_CHECK("bist_adam_step_dev");
+  BIST_LAUNCH_CHECK(who);
   return BIST_OK;
+}
+extern "C" int bist_adam_step_dev_bg(float* p, const void* g, float* m, float* v, void* work, int64_t n, const float* hyper, float beta1,
+                                     float beta2, float eps, int32_t grad_dtype, int32_t work_dtype, int32_t max_blocks, void* stream) {
+  return adam_step_dev_launch<false>(p, g, m, v, work, n, hyper, beta1, beta2, eps, grad_dtype, work_dtype, max_blocks, stream,
+                                     "bist_adam_step_dev", "bist_adam_step_dev_bg");
+}
+// bist_adam_step_dev_bg that declines to run when hyper[5] != 0 (the skip word of bist_clip_hyper, grad_norm.hip)
+extern "C" int bist_adam_step_dev_guard(float* p, const void* g, float* m, float* v, void* work, int64_t n, const float* hyper, float beta1,
+                                        float beta2, float eps, int32_t grad_dtype, int32_t work_dtype, int32_t max_blocks, void* stream) {
+  return adam_step_dev_launch<true>(p, g, m, v, work, n, hyper, beta1, beta2, eps, grad_dtype, work_dtype, max_blocks, stream,
+                                    "bist_adam_step_dev_guard", "bist_adam_step_dev_guard");
 }
 
 extern "C" int bist_noam_hyper_pending(int64_t* pending, float* hyper, float d_model, float factor, float warmup, float beta1, float beta2,
@@ -1140,30 +1160,44 @@ extern "C" int bist_adam_apply_dev(float* p, void* g, float* m, float* v, void* 
 
 // Adam over a group of backward passes (adam_accum4_kernel above): `phase` is one device int32, bit 0 = first pass of the group, bit 1 =
 // last.  max_blocks as in bist_adam_step_dev_bg.
-extern "C" int bist_adam_accum_dev(float* p, const void* g, float* acc, float* m, float* v, void* work, int64_t n, const float* hyper,
-                                   const int32_t* phase, float beta1, float beta2, float eps, int32_t grad_dtype, int32_t work_dtype,
-                                   int32_t max_blocks, void* stream) {
-  BIST_REQUIRE(p && g && acc && m && v && hyper && phase && n > 0 && max_blocks >= 0, "bist_adam_accum_dev: bad argument");
+template <bool GUARD>
+static int adam_accum_dev_launch(float* p, const void* g, float* acc, float* m, float* v, void* work, int64_t n, const float* hyper,
+                                 const int32_t* phase, float beta1, float beta2, float eps, int32_t grad_dtype, int32_t work_dtype,
+                                 int32_t max_blocks, void* stream, const char* who) {
+  BIST_REQUIRE(p && g && acc && m && v && hyper && phase && n > 0 && max_blocks >= 0, "%s: bad argument", who);
   hipStream_t st = (hipStream_t)stream;
   // whole 16-byte groups: four elements per thread
   const bool vec = n % 4 == 0 && ((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc) % 16 == 0 &&
                    (uintptr_t)g % (grad_dtype == BIST_BF16 ? 8 : 16) == 0 && (!work || (uintptr_t)work % (work_dtype == BIST_BF16 ? 8 : 16) == 0);
   unsigned grid = vec ? blocks_for(n / 4, 256) : blocks_for(n, 256);
   if (max_blocks > 0) {
-    BIST_REQUIRE(vec, "bist_adam_accum_dev: the background form needs whole 16-byte groups (n %% 4 == 0, aligned pointers)");
+    BIST_REQUIRE(vec, "%s: the background form needs whole 16-byte groups (n %% 4 == 0, aligned pointers)", who);
     if (grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
   }
 #define ADAM(TG, TW)                                                                                                                                  \
   do {                                                                                                                                                \
-    if (vec) hipLaunchKernelGGL((adam_accum4_kernel<TG, TW>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, acc, m, v, (TW*)work, (long)(n / 4), beta1, beta2, eps, hyper, (const int*)phase); \
-    else hipLaunchKernelGGL((adam_accum_kernel<TG, TW>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, acc, m, v, (TW*)work, (long)n, beta1, beta2, eps, hyper, (const int*)phase); \
+    if (vec) hipLaunchKernelGGL((adam_accum4_kernel<TG, TW, GUARD>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, acc, m, v, (TW*)work, (long)(n / 4), beta1, beta2, eps, hyper, (const int*)phase); \
+    else hipLaunchKernelGGL((adam_accum_kernel<TG, TW, GUARD>), dim3(grid), dim3(256), 0, st, p, (const TG*)g, acc, m, v, (TW*)work, (long)n, beta1, beta2, eps, hyper, (const int*)phase); \
   } while (0)
   if (grad_dtype == BIST_F32 && (work == nullptr || work_dtype == BIST_F32)) ADAM(float, float);
   else if (grad_dtype == BIST_F32 && work_dtype == BIST_BF16) ADAM(float, bf16_t);
   else if (grad_dtype == BIST_BF16 && (work == nullptr || work_dtype == BIST_BF16)) ADAM(bf16_t, bf16_t);
   else if (grad_dtype == BIST_BF16 && work_dtype == BIST_F32) ADAM(bf16_t, float);
-  else { bist_set_error("bist_adam_accum_dev: bad dtype combination"); return BIST_EINVAL; }
+  else { bist_set_error("%s: bad dtype combination", who); return BIST_EINVAL; }
 #undef ADAM
-  BIST_LAUNCH_CHECK("bist_adam_accum_dev");
+  BIST_LAUNCH_CHECK(who);
   return BIST_OK;
+}
+extern "C" int bist_adam_accum_dev(float* p, const void* g, float* acc, float* m, float* v, void* work, int64_t n, const float* hyper,
+                                   const int32_t* phase, float beta1, float beta2, float eps, int32_t grad_dtype, int32_t work_dtype,
+                                   int32_t max_blocks, void* stream) {
+  return adam_accum_dev_launch<false>(p, g, acc, m, v, work, n, hyper, phase, beta1, beta2, eps, grad_dtype, work_dtype, max_blocks, stream,
+                                      "bist_adam_accum_dev");
+}
+// bist_adam_accum_dev whose LAST pass declines to run Adam when hyper[5] != 0; first and middle passes accumulate as before
+extern "C" int bist_adam_accum_dev_guard(float* p, const void* g, float* acc, float* m, float* v, void* work, int64_t n, const float* hyper,
+                                         const int32_t* phase, float beta1, float beta2, float eps, int32_t grad_dtype, int32_t work_dtype,
+                                         int32_t max_blocks, void* stream) {
+  return adam_accum_dev_launch<true>(p, g, acc, m, v, work, n, hyper, phase, beta1, beta2, eps, grad_dtype, work_dtype, max_blocks, stream,
+                                     "bist_adam_accum_dev_guard");
 }

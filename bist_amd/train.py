@@ -24,7 +24,9 @@ from __future__ import annotations
 
 import collections
 import contextlib
+import ctypes
 import copy
+import math
 import os
 import time
 import re
@@ -91,6 +93,10 @@ MAX_EVAL_GRAPHS = 16
 # bist_eval_accumulate (include/bist_hip.h): at most BIST_EVAL_MAX_TERMS = 8 running totals per loss term; the integer totals are the
 # two token counts handed over (of at most BIST_EVAL_MAX_COUNTS = 4) plus the batch counter the launch appends: tokens, qtokens, batches
 EVAL_TERMS_MAX, EVAL_COUNTS = 8, 3
+# Trainer(max_grad_norm=...): partial slots (fp64) of the two bist_grad_sumsq launches of a step, fixed at construction -- the big matrices
+# [n32, numel) one workgroup per slot (1024 chunks of 128 K elements at BASELINE configs[1]: every CU holds several), then the prefix
+# [0, n32).  bist_clip_hyper adds the 1088 slots in index order (include/bist_hip.h: at most BIST_GRAD_SUMSQ_MAX_SLOTS in all).
+CLIP_SLOTS_BIG, CLIP_SLOTS_PREFIX = 1024, 64
 
 
 class _GraphEntry:
@@ -112,7 +118,8 @@ class Trainer:
                  warmup: int = 4000, factor: float = 1.0, smoothing: float = 0.1, pad: int = 1,
                  betas=(0.9, 0.98), eps: float = 1e-9, process_group=None, use_graph: bool = False,
                  deferred_adam: Optional[bool] = None, length_classes=None, max_graphs: int = MAX_GRAPHS,
-                 max_eval_graphs: int = MAX_EVAL_GRAPHS, deterministic: bool = False, accumulate: bool = False):
+                 max_eval_graphs: int = MAX_EVAL_GRAPHS, deterministic: bool = False, accumulate: bool = False,
+                 max_grad_norm: Optional[float] = None):
         self.model, self.args = model, args
         # Bit-reproducible steps: every pass of this trainer -- eager, capture warm-up, capture -- runs with
         # ops.DETERMINISTIC set, i.e. with the slab / owner reductions of det_reduce.hip in place of the float atomics of backward.hip.
@@ -177,6 +184,32 @@ class Trainer:
             if ADAM_CLEARS:
                 raise ValueError("Trainer(accumulate=True) refuses BIST_ADAM_CLEARS=1: the accumulating launch never writes the gradient buffer, "
                                  "the head of every pass clears it")
+        # Gradient norm, clip and non-finite guard inside the step: None = the trainer as it was (no buffer, no
+        # launch, the unguarded Adam).  A positive bound -- math.inf: measure and guard, never scale -- puts two bist_grad_sumsq launches and
+        # one bist_clip_hyper in front of the step's update, which becomes the guarded form: a step whose norm is not finite leaves the
+        # weights and both moments as they are and is counted in `self.skipped`.  Such a step still consumes its step number (drop_ctr /
+        # opt_ctr): the Noam rate, the bias corrections and the dropout masks move on.
+        # (kept as the C float bist_clip_hyper receives: a bound that float32 rounds to 0 or to +inf is refused here, not at the first step)
+        self.max_grad_norm = None if max_grad_norm is None else ctypes.c_float(float(max_grad_norm)).value
+        self.clip = self.max_grad_norm is not None
+        if self.clip:
+            if not self.max_grad_norm > 0.0:             # (NaN fails the comparison too)
+                raise ValueError("Trainer(max_grad_norm=%r): the bound must be positive as a float32 (math.inf: measure and guard, never scale)"
+                                 % (max_grad_norm,))
+            if math.isinf(self.max_grad_norm) and not math.isinf(float(max_grad_norm)):
+                raise ValueError("Trainer(max_grad_norm=%r): the bound must be positive and finite as a float32, or math.inf (measure and "
+                                 "guard, never scale)" % (max_grad_norm,))
+            if self.world > 1 or os.environ.get("BIST_FORCE_EXCHANGE") == "1":
+                raise ValueError("Trainer(max_grad_norm=...) refuses several ranks (and BIST_FORCE_EXCHANGE): the norm must be that of the "
+                                 "all-reduced gradient; it belongs with the exchange and is a separate change")
+            if deferred_adam:
+                raise ValueError("Trainer(max_grad_norm=...) refuses deferred_adam: the deferred update runs at the head of the next step, "
+                                 "whose bist_noam_hyper_pending rewrites the scalars the clip factor was written into")
+            if not self.adam_in_step:
+                raise ValueError("Trainer(max_grad_norm=...) refuses BIST_ADAM_IN_STEP=0: the update outside the step takes its scalars "
+                                 "from the host, not from the device buffer the clip factor is written into")
+            if ADAM_CLEARS:
+                raise ValueError("Trainer(max_grad_norm=...) refuses BIST_ADAM_CLEARS=1: the clearing update has no guarded form")
 
         params: List[torch.nn.Parameter] = []
         seen = set()
@@ -246,9 +279,16 @@ class Trainer:
         piece_lo = {pc: offs[id(q)] for pc, q in first_of_piece.items()}
         n_layers = max(piece_lo) if piece_lo else 0
         self.buckets: List[Tuple[int, int, int]] = []          # (cut layer, lo, hi)
-        self.early_adam = (self.adam_in_step and not self.deferred and use_graph and SPLIT_GRAPH and ADAM_EARLY_BUCKETS > 0 and not ADAM_CLEARS
-                           and dev.type == "cuda" and Fn.CONCURRENT)
-        nb = max(0, min(EXCHANGE_BUCKETS if self.exchanging else ADAM_EARLY_BUCKETS if self.early_adam else 0, n_layers - 1))
+        # early_marks: the captured step acts at the buckets' marks inside the backward pass -- the early bias / LayerNorm-parameter
+        # reductions (EARLY_REDUCTIONS, FLUSH_AT_0) and, with early_adam, the update of the bucket.  max_grad_norm switches early_adam OFF and
+        # keeps the marks: no bucket can be updated before the norm of the WHOLE gradient is known, so every Adam launch of such a step
+        # sits at the tail, behind bist_clip_hyper; the reductions do not depend on the norm and stay where they are.
+        self.early_marks = (self.adam_in_step and not self.deferred and use_graph and SPLIT_GRAPH and ADAM_EARLY_BUCKETS > 0 and not ADAM_CLEARS
+                            and dev.type == "cuda" and Fn.CONCURRENT)
+        # (early_adam is re-read by _bucket_adam when a step is captured: scripts/bench_clip.py clears it on a finished plain trainer, before
+        # its first capture, to time "the marks without the early update" -- keep that read there, or give the script a switch)
+        self.early_adam = self.early_marks and not self.clip
+        nb = max(0, min(EXCHANGE_BUCKETS if self.exchanging else ADAM_EARLY_BUCKETS if self.early_marks else 0, n_layers - 1))
         hi_ = n
         cuts_env = os.environ.get("BIST_BUCKET_CUTS")          # tuning aid: explicit cut layers, descending ("3,1")
         cuts = [int(c) for c in cuts_env.split(",")] if (cuts_env and nb) else [n_layers - (j + 1) * n_layers // (nb + 1) for j in range(nb)]
@@ -285,6 +325,11 @@ class Trainer:
             self.phase = torch.zeros(1, device=dev, dtype=torch.int32)
             self.opt_ctr = torch.zeros(1, device=dev, dtype=torch.int64)
             self._passes = 0
+        if self.clip:
+            # allocated here, before any capture: the fp64 partial slots of the step's two bist_grad_sumsq launches (every slot is
+            # rewritten by every measuring launch: no memset) and the count of skipped updates
+            self.clip_partials = torch.zeros(CLIP_SLOTS_BIG + CLIP_SLOTS_PREFIX, device=dev, dtype=torch.float64)
+            self.skipped = torch.zeros(1, device=dev, dtype=torch.int64)
         # slab workspaces of the deferred bias / LayerNorm-parameter reductions (ops.reduce_workspace, reduce_slab.hip), allocated here --
         # before any capture, so a replayed step finds them where it recorded them.  One per stream that flushes: the caption chain's
         # early flushes (_flush_on_caption_chain) and the closing flush on the step's own stream (_backward_close) may run side by side.
@@ -335,6 +380,7 @@ class Trainer:
         self.drop_ctr = torch.zeros(1, device=dev, dtype=torch.int64)
         ops.DROP_CTR = self.drop_ctr
         # ready flags of the buckets, in pinned host memory: 4 per bucket (one per stream of the step)
+        self.early_marks = self.early_marks and bool(self.buckets)
         self.early_adam = self.early_adam and bool(self.buckets)
         self._early_done = 0                                   # buckets updated inside the running backward pass
         self._early_armed = False                              # (set by backward(optimizer=True) around its pass)
@@ -376,22 +422,56 @@ class Trainer:
     def _adam_dev(self, lo: int, hi: int, max_blocks: int = 0) -> None:
         """Adam on flat elements [lo, hi) with this step's scalars read from ``self.hyper`` (device): capturable.  max_blocks > 0: as a
         background launch of that many workgroups (bist_adam_step_dev_bg).  accumulate=True: the same range through bist_adam_accum_dev,
-        which adds the pass's gradient into ``self.acc`` and runs Adam only in the last pass of a group (``self.phase``)."""
+        which adds the pass's gradient into ``self.acc`` and runs Adam only in the last pass of a group (``self.phase``).  max_grad_norm: the
+        guarded forms of both, which leave the weights and the moments alone when bist_clip_hyper has set the skip word hyper[5]."""
         if hi <= lo:
             return
         work = None if self.compute_dtype == torch.float32 else self.flat_param
         gsz = self.flat_grad.element_size()
         if self.accumulate:
-            check(lib.bist_adam_accum_dev(self.master.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + gsz * lo, self.acc.data_ptr() + 4 * lo,
-                                          self.m.data_ptr() + 4 * lo, self.v.data_ptr() + 4 * lo,
-                                          (work.data_ptr() + work.element_size() * lo) if work is not None else None, hi - lo,
-                                          self.hyper.data_ptr(), self.phase.data_ptr(), self.betas[0], self.betas[1], self.eps,
-                                          dtype_code(self.compute_dtype), dtype_code(self.compute_dtype), max_blocks, _stream()), "bist_adam_accum_dev")
+            name = "bist_adam_accum_dev_guard" if self.clip else "bist_adam_accum_dev"
+            check(getattr(lib, name)(self.master.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + gsz * lo, self.acc.data_ptr() + 4 * lo,
+                                     self.m.data_ptr() + 4 * lo, self.v.data_ptr() + 4 * lo,
+                                     (work.data_ptr() + work.element_size() * lo) if work is not None else None, hi - lo,
+                                     self.hyper.data_ptr(), self.phase.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                                     dtype_code(self.compute_dtype), dtype_code(self.compute_dtype), max_blocks, _stream()), name)
             return
-        check(lib.bist_adam_step_dev_bg(self.master.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + gsz * lo, self.m.data_ptr() + 4 * lo,
-                                        self.v.data_ptr() + 4 * lo, (work.data_ptr() + work.element_size() * lo) if work is not None else None,
-                                        hi - lo, self.hyper.data_ptr(), self.betas[0], self.betas[1], self.eps,
-                                        dtype_code(self.compute_dtype), dtype_code(self.compute_dtype), max_blocks, _stream()), "bist_adam_step_dev")
+        name = "bist_adam_step_dev_guard" if self.clip else "bist_adam_step_dev_bg"
+        check(getattr(lib, name)(self.master.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + gsz * lo, self.m.data_ptr() + 4 * lo,
+                                 self.v.data_ptr() + 4 * lo, (work.data_ptr() + work.element_size() * lo) if work is not None else None,
+                                 hi - lo, self.hyper.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                                 dtype_code(self.compute_dtype), dtype_code(self.compute_dtype), max_blocks, _stream()), name)
+
+    def _grad_sumsq(self, lo: int, hi: int, slot_lo: int, nslots: int) -> None:
+        """bist_grad_sumsq of flat elements [lo, hi) into the partial slots [slot_lo, slot_lo + nslots): capturable.  accumulate=True: of
+        acc + gradient (the gradient alone in a group of one), in the last pass of a group only (``self.phase``)."""
+        if hi <= lo:                     # (an empty range: its slots keep the zeros they were allocated with)
+            return
+        gsz = self.flat_grad.element_size()
+        check(lib.bist_grad_sumsq(self.flat_grad.data_ptr() + gsz * lo, (self.acc.data_ptr() + 4 * lo) if self.accumulate else None,
+                                  self.phase.data_ptr() if self.accumulate else None, hi - lo, dtype_code(self.compute_dtype),
+                                  self.clip_partials.data_ptr(), slot_lo, nslots, 0, _stream()), "bist_grad_sumsq")
+
+    def _clip_hyper(self) -> None:
+        """bist_clip_hyper over all partial slots: the step's norm, clip factor and skip word into ``self.hyper`` (slots 6, 7, 5; the
+        factor is folded into grad_scale, slot 3).  accumulate=True: in the last pass of a group only."""
+        check(lib.bist_clip_hyper(self.clip_partials.data_ptr(), self.clip_partials.numel(), self.max_grad_norm, self.hyper.data_ptr(),
+                                  self.skipped.data_ptr(), self.phase.data_ptr() if self.accumulate else None, _stream()), "bist_clip_hyper")
+
+    def grad_norm(self) -> torch.Tensor:
+        """The global norm of the gradient of the last finished update, before clipping, as a device scalar (a view of ``hyper[6]``: no
+        synchronisation; read it before the next step is queued, or clone it on the step's stream)."""
+        if not self.clip:
+            raise RuntimeError("Trainer.grad_norm needs a trainer built with max_grad_norm (math.inf measures without clipping)")
+        return self.hyper[6]
+
+    def clip_stats(self) -> Dict[str, float]:
+        """Synchronises: the norm and the clip factor of the last update (factor 0: it was skipped) and the number of updates skipped so
+        far because their gradient norm was not finite."""
+        if not self.clip:
+            raise RuntimeError("Trainer.clip_stats needs a trainer built with max_grad_norm (math.inf measures without clipping)")
+        h = self.hyper.tolist()
+        return {"norm": h[6], "scale": h[7], "skipped": int(self.skipped.item())}
 
     def _adam_apply(self, lo: int, hi: int) -> None:
         """bist_adam_apply_dev on flat elements [lo, hi): Adam with ``self.hyper`` (skipped when nothing is pending) + clear of the gradient."""
@@ -503,7 +583,7 @@ class Trainer:
             for st in Fn.step_streams(self._main_stream):
                 if st.cuda_stream != cap.cuda_stream:
                     cap.wait_stream(st)
-        if j is None:
+        if j is None or not self.early_adam:      # (max_grad_norm: the marks flush reductions only, every update waits for the norm)
             return
         with torch.cuda.stream(cap):
             STM.mark("early adam %d" % j) if STM.ENABLED else None
@@ -613,13 +693,15 @@ class Trainer:
                                       float(self.warmup), self.betas[0], self.betas[1], 1.0, _stream()), "bist_noam_hyper")
         # one rank, optimiser in the step: Adam clears every gradient it consumes (bist_adam_apply_dev), so a REPLAYED step starts from a
         # clean buffer without a memset of its own (_graph_open clears it when something else left a gradient behind)
-        self._early_armed = bool(optimizer and self.early_adam)
+        self._early_armed = bool(optimizer and self.early_marks)
         try:
             terms = self._backward_open(batch, clear=not (optimizer and self._skip_head_clear))
         finally:
             self._early_armed = False
         big_end = self.buckets[self._early_done - 1][1] if self._early_done else self.numel      # (the buckets above were updated inside the pass)
         side = None
+        if optimizer and self.clip:
+            return self._clipped_tail(terms)
         if optimizer and self.flat_grad.is_cuda:
             main, side = torch.cuda.current_stream(), Fn.side_stream(0)
             side.wait_stream(main)
@@ -637,6 +719,27 @@ class Trainer:
                 self._adam_dev(0, self.numel)
         else:
             self._dirty = True
+        return terms
+
+    def _clipped_tail(self, terms):
+        """The tail of a step with max_grad_norm: the sum of squares of the big matrices on the side stream BESIDE the closing reductions
+        (where Adam runs otherwise), the closing reductions, the sum of squares of the prefix -- of the bf16 gradient after
+        bist_add_f32_into, i.e. of what Adam reads -- then, behind the join, bist_clip_hyper and ONE guarded Adam over everything.
+        No host synchronisation: capturable, one graph per class as before."""
+        if not self.flat_grad.is_cuda:
+            raise RuntimeError("Trainer(max_grad_norm=...): the norm, the clip factor and the guarded update are device launches "
+                               "(bist_grad_sumsq, bist_clip_hyper); a trainer on %s cannot step with the option" % self.flat_grad.device)
+        main, side = torch.cuda.current_stream(), Fn.side_stream(0)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            self._grad_sumsq(self.n32, self.numel, 0, CLIP_SLOTS_BIG)
+        self._backward_close()
+        STM.mark("closing reductions done")
+        self._grad_sumsq(0, self.n32, CLIP_SLOTS_BIG, CLIP_SLOTS_PREFIX)
+        main.wait_stream(side)
+        self._clip_hyper()
+        self._adam_dev(0, self.numel)
+        STM.mark("step end")
         return terms
 
     # ---- hipGraph path: forward + backward + gradient fold captured once per batch geometry ----------------

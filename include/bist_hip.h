@@ -673,6 +673,39 @@ int bist_adam_step_dev_bg(float* p, const void* g, float* m, float* v, void* wor
 int bist_adam_accum_dev(float* p, const void* g, float* acc, float* m, float* v, void* work, int64_t n, const float* hyper,
                         const int32_t* phase, float beta1, float beta2, float eps, int32_t grad_dtype, int32_t work_dtype,
                         int32_t max_blocks, void* stream);
+/* Gradient norm, clip and non-finite guard inside the step (Trainer(max_grad_norm=...)).  The reference neither
+ * clips nor guards (train.py:29-37, optimize.py:19-26); the factor is that of torch.nn.utils.clip_grad_norm_.
+ *
+ * bist_grad_sumsq: partials[slot_lo + s] = sum of squares (fp64) of chunk s of the n elements at g, s = 0 .. nslots - 1.  The chunk
+ * length is ceil(n / nslots) rounded up to a multiple of 8 elements -- a function of (n, nslots) alone; a slot whose chunk is empty
+ * receives 0.0, every slot is written by every launch (no memset).  No atomics: within a chunk each thread adds a fixed strided sequence
+ * of elements in fp64 and a fixed tree combines the workgroup, so the slots' bits do not depend on the grid, on max_blocks (> 0: at most
+ * that many workgroups walk the slots; 0: one workgroup per slot) or on the order of arrival.  16-byte loads from the first 16-byte line
+ * of g on, scalar head and tail: besides the data and (n, nslots) the bits DO depend on the offset of g within a 16-byte line (the
+ * length of the head decides which of a thread's chains an element is added to) -- equal for a caller whose ranges stay where they are.  acc (fp32, n elements) and phase (the device word of bist_adam_accum_dev) are given together or both
+ * NULL: with phase bit 1 (last pass) clear the launch stores nothing; otherwise the summed value is g when bit 0 is set, else acc + g
+ * formed in fp32 as bist_adam_accum_dev forms it.  1 <= nslots, slot_lo + nslots <= BIST_GRAD_SUMSQ_MAX_SLOTS.
+ *
+ * bist_clip_hyper (one workgroup): sum = partials[0] + .. + partials[nslots_total - 1] in index order (fp64),
+ *   norm = (float)sqrt(sum) * hyper[3]   -- the norm of the gradient as Adam will consume it (hyper[3] = grad_scale)
+ *   finite:      hyper[5] = 0, hyper[6] = norm, hyper[7] = scale = min(1, max_norm / (norm + 1e-6f)), hyper[3] *= scale
+ *   not finite:  hyper[5] = 1, hyper[6] = norm, hyper[7] = 0, hyper[3] untouched, skipped_ctr[0] += 1 (device int64)
+ * max_norm = +inf leaves hyper[3] bit for bit.  With phase given and its bit 1 clear: hyper[5] = 0 and nothing else.  max_norm must be
+ * positive (NaN is refused), 1 <= nslots_total <= BIST_GRAD_SUMSQ_MAX_SLOTS.
+ *
+ * bist_adam_step_dev_guard / bist_adam_accum_dev_guard: bist_adam_step_dev_bg / bist_adam_accum_dev that return at their head, leaving
+ * p, m, v, work (and acc) as they are, when hyper[5] != 0 -- the accumulating form in the last pass of a group only.  With
+ * hyper[5] == 0 the bits of the unguarded launches.                                                                             */
+#define BIST_GRAD_SUMSQ_MAX_SLOTS 4096
+int bist_grad_sumsq(const void* g, const float* acc, const int32_t* phase, int64_t n, int32_t grad_dtype, double* partials,
+                    int32_t slot_lo, int32_t nslots, int32_t max_blocks, void* stream);
+int bist_clip_hyper(const double* partials, int32_t nslots_total, float max_norm, float* hyper, int64_t* skipped_ctr,
+                    const int32_t* phase, void* stream);
+int bist_adam_step_dev_guard(float* p, const void* g, float* m, float* v, void* work, int64_t n, const float* hyper, float beta1,
+                             float beta2, float eps, int32_t grad_dtype, int32_t work_dtype, int32_t max_blocks, void* stream);
+int bist_adam_accum_dev_guard(float* p, const void* g, float* acc, float* m, float* v, void* work, int64_t n, const float* hyper,
+                              const int32_t* phase, float beta1, float beta2, float eps, int32_t grad_dtype, int32_t work_dtype,
+                              int32_t max_blocks, void* stream);
 /* Deferred form: the update of optimiser step t is applied at the HEAD of step t+1, beside its forward pass (the tail of a step is
  * then the backward pass alone).  bist_noam_hyper_pending reads t = pending[0] (device int64; 0 = nothing pending), writes
  * hyper[0..4] = {rate(t), 1 - beta1^t, 1 - beta2^t, grad_scale, apply = (t > 0)} and sets pending[0] = 0; the caller sets
