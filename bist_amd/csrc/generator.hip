@@ -105,8 +105,8 @@ __global__ __launch_bounds__(256) void text_vector_kernel(const float* __restric
 
 // The switch logits of (Multi)PointerGenerator (generator.py:71, 119-121): pointer_gen_W applied to the concatenation of n_parts <= 4
 // [rows, d] tensors WITHOUT the concatenation -- part j multiplies column block j of W [ns <= 4][n_parts d].  One launch forward (a wave
-// per row) and two backward (the parts' gradients: a wave per row; the weight / bias gradient: a workgroup per part, four row slices
-// per workgroup) where a product per part took 4 launches forward and 12 backward (cast + dX + dW each).
+// per row) and two backward (the parts' gradients: a wave per row; the weight / bias gradient: a workgroup per part and 64 four-byte column
+// pieces, sixteen row slices per workgroup) where a product per part took 4 launches forward and 12 backward (cast + dX + dW each).
 struct SwParts { const void* x[4]; void* dx[4]; const void* res[4]; int n; };
 
 template <typename T, typename TO>
@@ -183,74 +183,78 @@ __global__ __launch_bounds__(256) void switch_logits_bwd_x_kernel(SwParts a, con
   }
 }
 
-// dW[s][j d + c] (+)= sum_rows dsw[row][s] part_j[row][c];  db[s] (+)= sum_rows dsw[row][s].  blockIdx.x = part, blockIdx.y = chunk of 64 E
-// columns; thread = (column piece lane, row slice sl): the four slices meet in LDS.
+// dW[s][j d + c] (+)= sum_rows dsw[row][s] part_j[row][c];  db[s] (+)= sum_rows dsw[row][s].  blockIdx.x = part, blockIdx.y = chunk of 64
+// 4-byte column pieces (128 bf16 / 64 f32 columns); thread = (column piece lane, row slice sl): 16 slices of ceil(rows / 16) consecutive
+// rows, one wave each, 16 rows' loads in flight per step.  The slices meet in LDS and are added in slice order by the ONE thread that owns
+// the dW element (no atomics, nothing between workgroups: the order of the sum follows from rows alone).  The wave reads the <= 64 dsw
+// values of a step once (lane l holds value l) and hands them out by readlane.  At rows = 320, d = 512, four bf16 parts: 16 workgroups of
+// 16 waves, two steps each, where four workgroups of four waves walked ten.
+constexpr int SWW_SLICES = 16, SWW_ROWS = 16;
 template <typename T, typename TW, typename TS>
-__global__ __launch_bounds__(256) void switch_logits_bwd_w_kernel(SwParts a, const TS* __restrict__ dsw, TW* __restrict__ dW, long lddw, int dw_acc,
-                                                                  float* __restrict__ db, int db_acc, long rows, int d, int ns) {
-  constexpr int E = 16 / (int)sizeof(T);
-  __shared__ float part[3][64][4][E];
-  const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6, j = blockIdx.x;
-  const int c = (blockIdx.y * 64 + lane) * E;
+__global__ __launch_bounds__(64 * SWW_SLICES) void switch_logits_bwd_w_kernel(SwParts a, const TS* __restrict__ dsw, TW* __restrict__ dW, long lddw,
+                                                                              int dw_acc, float* __restrict__ db, int db_acc, long rows, int d, int ns) {
+  constexpr int P = 4 / (int)sizeof(T);       // columns of one lane
+  constexpr int CW = 64 * P;                  // columns of one workgroup
+  static_assert(4 * CW <= 64 * SWW_SLICES && SWW_ROWS * 4 <= 64, "one writer thread per (logit, column); a step's dsw values fit one wave");
+  __shared__ float part[SWW_SLICES][4][CW];
+  __shared__ float bpart[SWW_SLICES][4];
+  const int lane = threadIdx.x & 63, sl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = blockIdx.x;
+  const int cb = blockIdx.y * CW, c = cb + lane * P;
   const bool act = c < d;
+  // the thread that writes dW[os][j d + oc] fetches what it adds to ahead of the row loop
+  const int os = threadIdx.x / CW, oc = cb + threadIdx.x % CW;
+  const bool writer = os < ns && oc < d;
+  TW* dst = dW + (long)os * lddw + (long)j * d + oc;
+  const float old = (writer && dw_acc) ? to_f(*dst) : 0.f;
   const T* xb = reinterpret_cast<const T*>(a.x[j]);
-  float acc[4][E];
+  float acc[4][P];
 #pragma unroll
   for (int s_ = 0; s_ < 4; ++s_)
 #pragma unroll
-    for (int e = 0; e < E; ++e) acc[s_][e] = 0.f;
+    for (int e = 0; e < P; ++e) acc[s_][e] = 0.f;
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-  const long per = (rows + 3) / 4, r0 = sl * per, r1 = min(rows, r0 + per);
-  // eight rows per step: their loads are in flight together (one row per step made this a chain of ~80 dependent round trips)
-  for (long rb = r0; rb < r1; rb += 8) {
-    uint4 xq[8];
-    float g[8][4];
+  const long per = (rows + SWW_SLICES - 1) / SWW_SLICES, r0 = sl * per, r1 = min(rows, r0 + per);
+  for (long rb = r0; rb < r1; rb += SWW_ROWS) {
+    unsigned xq[SWW_ROWS];
+    // every load is issued (a row past the slice re-reads the slice's last row, an idle lane column 0) and masked afterwards: a load
+    // under a condition would be branched around and waited for one by one
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const long r = rb + u;
-      const bool ok = r < r1;
-      xq[u] = (ok && act) ? *reinterpret_cast<const uint4*>(xb + r * d + c) : make_uint4(0u, 0u, 0u, 0u);
+    for (int u = 0; u < SWW_ROWS; ++u) xq[u] = *reinterpret_cast<const unsigned*>(xb + min(rb + u, r1 - 1) * d + (act ? c : 0));
 #pragma unroll
-      for (int s_ = 0; s_ < 4; ++s_) g[u][s_] = (ok && s_ < ns) ? to_f(dsw[r * ns + s_]) : 0.f;
-    }
+    for (int u = 0; u < SWW_ROWS; ++u) xq[u] = rb + u < r1 ? xq[u] : 0u;
+    const long gi = rb * ns + lane;
+    const float gv = (lane < SWW_ROWS * ns && gi < r1 * ns) ? to_f(dsw[gi]) : 0.f;       // rows past the slice count as zero
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
+    for (int u = 0; u < SWW_ROWS; ++u) {
       const T* xv = reinterpret_cast<const T*>(&xq[u]);
 #pragma unroll
       for (int s_ = 0; s_ < 4; ++s_) {
+        // logit s_ >= ns reads lane 63, which holds zero whenever ns < 4 (a select of the lane, not a branch round the read)
+        const float g = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, gv), s_ < ns ? u * ns + s_ : 63));
 #pragma unroll
-        for (int e = 0; e < E; ++e) acc[s_][e] += g[u][s_] * to_f(xv[e]);
-        bsum[s_] += g[u][s_];
+        for (int e = 0; e < P; ++e) acc[s_][e] += g * to_f(xv[e]);
+        bsum[s_] += g;
       }
     }
   }
-  if (sl > 0) {
 #pragma unroll
-    for (int s_ = 0; s_ < 4; ++s_)
+  for (int s_ = 0; s_ < 4; ++s_) {
 #pragma unroll
-      for (int e = 0; e < E; ++e) part[sl - 1][lane][s_][e] = acc[s_][e];
+    for (int e = 0; e < P; ++e) part[sl][s_][lane * P + e] = acc[s_][e];
+    if (lane == 0) bpart[sl][s_] = bsum[s_];
   }
-  __shared__ float bpart[4][4];
-  if (lane == 0)
-#pragma unroll
-    for (int s_ = 0; s_ < 4; ++s_) bpart[sl][s_] = bsum[s_];
   __syncthreads();
-  if (sl == 0 && act) {
+  if (writer) {
+    float v = part[0][os][threadIdx.x % CW];
 #pragma unroll
-    for (int s_ = 0; s_ < 4; ++s_) {
-      if (s_ < ns) {
-        TW* dst = dW + (long)s_ * lddw + (long)j * d + c;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          const float v = acc[s_][e] + part[0][lane][s_][e] + part[1][lane][s_][e] + part[2][lane][s_][e];
-          dst[e] = from_f<TW>(dw_acc ? to_f(dst[e]) + v : v);
-        }
-      }
-    }
+    for (int q = 1; q < SWW_SLICES; ++q) v += part[q][os][threadIdx.x % CW];
+    *dst = from_f<TW>(dw_acc ? old + v : v);
   }
   if (db && j == 0 && blockIdx.y == 0 && threadIdx.x < ns) {
     const int s_ = threadIdx.x;
-    const float v = bpart[0][s_] + bpart[1][s_] + bpart[2][s_] + bpart[3][s_];
+    float v = bpart[0][s_];
+#pragma unroll
+    for (int q = 1; q < SWW_SLICES; ++q) v += bpart[q][s_];
     db[s_] = db_acc ? db[s_] + v : v;
   }
 }
@@ -725,8 +729,9 @@ extern "C" int bist_switch_logits_bwd(const void* const* parts, int32_t n_parts,
     BIST_LAUNCH_CHECK("bist_switch_logits_bwd (parts)");
   }
   if (dW) {
-    dim3 grid((unsigned)n_parts, (unsigned)((d / e + 63) / 64));
-#define SWW(TT, TWW, TSS) hipLaunchKernelGGL((switch_logits_bwd_w_kernel<TT, TWW, TSS>), grid, dim3(256), 0, st, a, (const TSS*)dsw, (TWW*)dW, (long)lddw, dw_accumulate, db, db_accumulate, (long)rows, d, ns)
+    const int cw = dtype == BIST_BF16 ? 128 : 64;                              // columns per workgroup: 64 four-byte pieces
+    dim3 grid((unsigned)n_parts, (unsigned)((d + cw - 1) / cw));
+#define SWW(TT, TWW, TSS) hipLaunchKernelGGL((switch_logits_bwd_w_kernel<TT, TWW, TSS>), grid, dim3(64 * SWW_SLICES), 0, st, a, (const TSS*)dsw, (TWW*)dW, (long)lddw, dw_accumulate, db, db_accumulate, (long)rows, d, ns)
     if (dtype == BIST_BF16) {
       if (dw_dtype == BIST_BF16) { if (s32) SWW(bf16_t, bf16_t, float); else SWW(bf16_t, bf16_t, bf16_t); }
       else { if (s32) SWW(bf16_t, float, float); else SWW(bf16_t, float, bf16_t); }

@@ -114,6 +114,7 @@ DETERMINISTIC = False
 _DET_WS = {}
 DET_WORKSPACE_BYTES = 16 << 20
 _SPLIT64 = 4              # BIST_GEMM_SPLIT64 (include/bist_hip.h): split-K combined inside the launch by whichever workgroup arrives last
+GEMM_RING64 = 8           # BIST_GEMM_RING64 (include/bist_hip.h): a long-K product on few tiles keeps the 64x64 ring kernel (same bits as the 32x32 one)
 
 
 def _det_workspace(device) -> Tensor:

@@ -147,6 +147,8 @@ int bist_gemm_ln_ok(const BistGemm* g);       /* 1 if bist_gemm(g) will run g's 
 #define BIST_GEMM_SPLIT64 4   /* hint bit: cut a long K of a small 64-tile product over neighbouring workgroups and combine
                                * them inside the launch (agent-scope release / ticket / acquire); measured slower than the
                                * unsplit ring kernel on this model's shapes, so never chosen automatically              */
+#define BIST_GEMM_RING64 8    /* hint bit: a long-K product on at most 64 tiles of 64x64 keeps the 64x64 ring kernel instead of
+                               * the 32x32 one that is chosen automatically (same bits either way: tests, tuning)          */
 
 int bist_gemm(const BistGemm* g, void* stream);
 /* Two independent products in one call.  When they are the backward pair of a linear layer on few rows -- a: dX = dZ.W
