@@ -13,7 +13,7 @@ F32, BF16 = 0, 1
 GRAD_SUMSQ_MAX_SLOTS = 4096      # BIST_GRAD_SUMSQ_MAX_SLOTS (include/bist_hip.h)
 ACT_NONE, ACT_RELU, ACT_GATE = 0, 1, 2
 # kernel families of bist_launch_count (include/bist_hip.h: BIST_K_*)
-K_ST1_MFMA_FWD, K_ST1_MFMA_BWD, K_ST1_VALU, K_ST2_MFMA_FWD, K_ST2_MFMA_BWD, K_ST2_VALU, K_MHA_FWD, K_MHA_BWD_MFMA, K_MHA_BWD_VALU, K_ST1_FUSED, K_DECSTACK, K_ST1_FUSED_TRAIN, K_ST1_PBWD = range(13)
+K_ST1_MFMA_FWD, K_ST1_MFMA_BWD, K_ST1_VALU, K_ST2_MFMA_FWD, K_ST2_MFMA_BWD, K_ST2_VALU, K_MHA_FWD, K_MHA_BWD_MFMA, K_MHA_BWD_VALU, K_ST1_FUSED, K_DECSTACK, K_ST1_FUSED_TRAIN, K_ST1_PBWD, K_MHA_FWD_DK64 = range(14)
 
 
 class BistGemm(C.Structure):

@@ -14,6 +14,7 @@
 namespace {
 
 constexpr float MASK_FILL = -1e9f;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 // ---------------------------------------------------------------------------------------------
 // mha_core: block = 4 waves, each wave owns one (n, hh, i) row.
@@ -86,6 +87,87 @@ __global__ __launch_bounds__(256) void mha_core_kernel(const T* __restrict__ Q, 
     for (int j = 0; j < Lk; ++j) acc += ps[j] * to_f(Vn[(long)j * ldv + c]);
     o[c] = from_f<T>(acc);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// mha_core in bf16 at dk = 64, Lk <= 64 (the query / caption / decoder attention of the training step): the same sums in the same
+// order as mha_core_kernel, with every operand fetched ahead.  Each lane issues its whole key row (64 / E 16-byte pieces),
+// its share of the (n, hh) value tile (NT pieces: PPR lanes per row, 64 / PPR rows per trip) and its mask byte before the
+// first wait; nothing is loaded under a condition (rows >= Lk re-read row Lk - 1, a wave past the last item re-reads the
+// last item).  The value tile waits in registers while the scores and the softmax run, then goes to the wave's LDS tile,
+// from where P.V reads it with j ascending.
+// LDS per wave: q (64 floats), probabilities (Lk rounded up to 4 floats), value tile [Lk][64] of T.
+// ---------------------------------------------------------------------------------------------
+template <typename T, int NT>
+__global__ __launch_bounds__(256) void mha_core_dk64_kernel(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ V,
+                                                            const unsigned char* __restrict__ mask, T* __restrict__ O, float* __restrict__ P,
+                                                            int N, int Lq, int Lk, int h, long ldq, long ldk, long ldv, long ldo,
+                                                            long q_bs, long k_bs, long v_bs, long o_bs, long mask_bs, long mask_qs, float scale,
+                                                            const DropArg drop) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int dk = 64, E = 16 / (int)sizeof(T), PPR = dk / E, RPT = 64 / PPR;      // pieces per row, value rows per trip
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long item = (long)blockIdx.x * 4 + w;
+  const long total = (long)N * h * Lq;
+  const int LkP = (Lk + 3) & ~3;
+  const long wave_floats = dk + LkP + (long)Lk * dk * (long)sizeof(T) / 4;
+  float* qs = smem + w * wave_floats;
+  float* ps = qs + dk;
+  T* vs = reinterpret_cast<T*>(ps + LkP);
+  const bool active = item < total;
+  const long it = active ? item : total - 1;
+  const int i = (int)(it % Lq);
+  const long t2 = it / Lq;
+  const int hh = (int)(t2 % h), n = (int)(t2 / h);
+  const T* Kn = K + n * k_bs + hh * dk;
+  const T* Vn = V + n * v_bs + hh * dk;
+  const unsigned char* mrow = mask ? mask + n * mask_bs + (long)i * mask_qs : reinterpret_cast<const unsigned char*>(Kn);
+  const int jc = min(lane, Lk - 1);
+  // ---- every global load of the wave, back to back ----
+  const T qv = Q[n * q_bs + (long)i * ldq + hh * dk + lane];
+  u32x4 kp[PPR], vp[NT];                               // (native vectors: arrays of the uint4 struct end up in scratch memory)
+  const T* kr = Kn + (long)jc * ldk;
+#pragma unroll
+  for (int c = 0; c < PPR; ++c) kp[c] = *reinterpret_cast<const u32x4*>(kr + c * E);
+  const unsigned char mbyte = mrow[jc];
+  const int vrow = lane / PPR, vcol = (lane % PPR) * E;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) vp[t] = *reinterpret_cast<const u32x4*>(Vn + (long)min(vrow + RPT * t, Lk - 1) * ldv + vcol);
+  __builtin_amdgcn_sched_barrier(0);                    // keep the loads together: the scheduler may not sink them towards their uses
+  qs[lane] = to_f(qv);
+  __syncthreads();
+  // one straight line from here on (a wave past the last item and lanes >= Lk compute on the clamped rows and store nothing): an early
+  // exit or a branch around the scores would let the compiler sink the loads above into it, back behind the first wait
+  const bool kv = lane < Lk;
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < PPR; ++c) {
+    T k8[E];
+    *reinterpret_cast<u32x4*>(k8) = kp[c];
+#pragma unroll
+    for (int e = 0; e < E; ++e) s += qs[c * E + e] * to_f(k8[e]);
+  }
+  s *= scale;
+  if (mask && mbyte == 0) s = MASK_FILL;
+  const float mx = wave_max(kv ? fmaxf(-INFINITY, s) : -INFINITY);
+  const float ex = kv ? expf(s - mx) : 0.f;
+  const float den = wave_sum(0.f + ex);
+  const float inv = 1.f / den;
+  if (kv) ps[lane] = ex * inv;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    if (vrow + RPT * t < Lk) *reinterpret_cast<u32x4*>(vs + (vrow + RPT * t) * dk + vcol) = vp[t];
+  __builtin_amdgcn_wave_barrier();
+  if (P && active && kv) P[(((long)n * h + hh) * Lq + i) * Lk + lane] = ps[lane];
+  if (drop.p > 0.f) {                                   // p_attn = dropout(p_attn), modules.py:62-63
+    const unsigned long long key = drop.key(), base = (unsigned long long)it * Lk;
+    const float ks = drop.keep_scale();
+    if (kv) ps[lane] *= drop_mul(key, base + lane, drop.p, ks);
+    __builtin_amdgcn_wave_barrier();
+  }
+  float acc = 0.f;
+  for (int j = 0; j < Lk; ++j) acc += ps[j] * to_f(vs[j * dk + lane]);
+  if (active) O[n * o_bs + (long)i * ldo + hh * dk + lane] = from_f<T>(acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -263,6 +345,22 @@ extern "C" int bist_mha_core_fwd(const void* Q, const void* K, const void* V, co
   const unsigned g = (unsigned)((items + 3) / 4);
   const long esz = dtype == BIST_BF16 ? 2 : 4, piece = 16 / esz;
   const int kvec = ((uintptr_t)K % 16 == 0) && ldk % piece == 0 && k_bs % piece == 0 && dk % piece == 0;
+  // dk = 64 and at most 64 keys whose rows come apart into 16-byte pieces: every operand is fetched ahead (mha_core_dk64_kernel)
+  const int vvec = ((uintptr_t)V % 16 == 0) && ldv % piece == 0 && v_bs % piece == 0;
+  const size_t lds_fast = (size_t)4 * ((size_t)(64 + ((Lk + 3) & ~3)) * sizeof(float) + (size_t)Lk * 64 * esz);
+  if (dtype == BIST_BF16 && dk == 64 && Lk <= 64 && kvec && vvec && lds_fast <= 64 * 1024) {
+    const int trips = (Lk + 7) / 8;                      // value rows go eight at a time
+#define MHA_FAST(NT_)                                                                                                                      \
+  hipLaunchKernelGGL((mha_core_dk64_kernel<bf16_t, NT_>), dim3(g), dim3(256), lds_fast, st, (const bf16_t*)Q, (const bf16_t*)K,           \
+                     (const bf16_t*)V, mask, (bf16_t*)O, p_attn, N, Lq, Lk, h, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, mask_bs, mask_qs, \
+                     scale, dr)
+    if (trips <= 1) MHA_FAST(1); else if (trips <= 2) MHA_FAST(2); else if (trips <= 4) MHA_FAST(4); else MHA_FAST(8);
+#undef MHA_FAST
+    BIST_LAUNCH_CHECK("bist_mha_core_fwd");
+    bist_count_launch(BIST_K_MHA_FWD);
+    bist_count_launch(BIST_K_MHA_FWD_DK64);
+    return BIST_OK;
+  }
   if (dtype == BIST_BF16)
     hipLaunchKernelGGL(mha_core_kernel<bf16_t>, dim3(g), dim3(256), lds, st, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V, mask,
                        (bf16_t*)O, p_attn, N, Lq, Lk, h, dk, ldq, ldk, ldv, ldo, q_bs, k_bs, v_bs, o_bs, mask_bs, mask_qs, scale, dr, kvec);

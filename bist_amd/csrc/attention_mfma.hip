@@ -541,6 +541,13 @@ __device__ __forceinline__ uint4 sfrag_cols(const bf16_t* img, int pitch, int co
   return r;
 }
 
+// v or zeros, component-wise (a ternary on the uint4 struct turns into an address select through scratch memory)
+__device__ __forceinline__ uint4 keep4(uint4 v, bool keep) {
+  const unsigned m = keep ? 0xffffffffu : 0u;
+  v.x &= m; v.y &= m; v.z &= m; v.w &= m;
+  return v;
+}
+
 struct St2Args {
   const bf16_t* q2f; const bf16_t* Y; const unsigned char* gmask;
   bf16_t* PY;                                         // forward
@@ -558,11 +565,47 @@ __device__ __forceinline__ uint4 k16_only(uint4 v, int lane) {
   return v;
 }
 
-// HALF (forward, G <= 32: the s2t direction at T = 32): 32-row images -- 42 KiB of LDS instead of 74, THREE workgroups per CU instead of
-// two (the B = 64 launch of 1 280 workgroups then takes two rounds of shorter workgroups instead of three), half the staging.
+// Staging of both images with every global load of the thread issued before the first LDS store: one wait for the whole
+// batch instead of one memory round trip per 16-byte piece (DC = d / 128 makes the trip counts compile-time).  No load sits
+// under a condition: rows >= G re-read row G - 1 (inside the tensor), head rows >= h re-read head h - 1, and both are zeroed
+// in registers afterwards (keep4).
+template <int GP, int QROWS, int DC>
+__device__ __forceinline__ void st2_stage(bf16_t* yimg, bf16_t* qg, const bf16_t* Yb, long ystride, const bf16_t* q2f,
+                                          const bf16_t* dpy, int G, int h, int tid) {
+  constexpr int CPR = 16 * DC, D = 128 * DC;                       // 16-byte chunks per row, row length
+  constexpr int NY = GP * CPR / 256, NQ = (QROWS * CPR + 255) / 256;
+  uint4 vy[NY], vq[NQ];
+#pragma unroll
+  for (int t = 0; t < NY; ++t) {
+    const int idx = tid + 256 * t, row = idx / CPR, c = idx - row * CPR;
+    vy[t] = *reinterpret_cast<const uint4*>(Yb + min(row, G - 1) * ystride + c * 8);
+  }
+#pragma unroll
+  for (int t = 0; t < NQ; ++t) {                                   // rows 0-7 q2f, (backward) rows 8-15 dPY: one load, source picked by address
+    const int idx = tid + 256 * t, row = idx / CPR, c = idx - row * CPR;
+    const bf16_t* src = (QROWS == 16 && (row & 8)) ? dpy : q2f;
+    vq[t] = *reinterpret_cast<const uint4*>(src + (long)min(row & 7, h - 1) * D + c * 8);
+  }
+  __builtin_amdgcn_sched_barrier(0);                               // the scheduler would otherwise pull the stores up between the loads to save registers
+#pragma unroll
+  for (int t = 0; t < NY; ++t) {
+    const int idx = tid + 256 * t, row = idx / CPR, c = idx - row * CPR;
+    *reinterpret_cast<uint4*>(yimg + row * D + ((c ^ (row & 7)) << 3)) = keep4(vy[t], row < G);
+  }
+#pragma unroll
+  for (int t = 0; t < NQ; ++t) {
+    const int idx = tid + 256 * t, row = idx / CPR, c = idx - row * CPR;
+    if (QROWS * CPR % 256 == 0 || idx < QROWS * CPR)
+      *reinterpret_cast<uint4*>(qg + row * D + ((c ^ (row & 7)) << 3)) = keep4(vq[t], (row & 7) < h);
+  }
+}
+
+// HALF (G <= 32: the s2t direction at T = 32): 32-row images -- forward 42 KiB of LDS instead of 74, THREE workgroups per CU instead of
+// two (the B = 64 launch of 1 280 workgroups then takes two rounds of shorter workgroups instead of three), half the staging; backward
+// 51 KiB instead of 86, three workgroups per CU instead of one (the 320 workgroups of B = 16 are then in flight at once).
 template <bool BWD, int GB, bool HALF = false>    // GB = 64-key blocks: G <= 64 GB (GB = 2: T = 128, BASELINE configs[3])
 __global__ __launch_bounds__(256) void st2_mfma_kernel(const St2Args a) {
-  static_assert(!HALF || (!BWD && GB == 1), "the 32-key form is a forward form");
+  static_assert(!HALF || GB == 1, "the 32-key form has one key block");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int GP = HALF ? 32 : 64 * GB;                          // padded key count = pitch of the score / probability images
   const int G = a.G, Lq = a.Lq, h = a.h, d = a.d;
@@ -576,23 +619,31 @@ __global__ __launch_bounds__(256) void st2_mfma_kernel(const St2Args a) {
   float* dpf = scf + 8 * GP;                                       // [8][GP] dP -> dS          (backward)
   bf16_t* pimg = reinterpret_cast<bf16_t*>(dpf + (BWD ? 8 * GP : 0));   // [16][GP]: rows 0-7 A-operand of PY / dq2f (P or dS);
                                                                    //           backward: rows 0-7 dS, 8-15 P
-  const int cpr = d >> 3;                                          // 16-byte chunks per row
   const long qoff = ((long)b * Lq + i) * h * d;
   const long ystride = (long)Lq * d;
   const bf16_t* Yb = a.Y + ((long)b * G * Lq + i) * d;
-  // ---- stage the images ---------------------------------------------------------------------------------
-  for (int idx = tid; idx < GP * cpr; idx += 256) {
-    const int row = idx / cpr, c = idx - row * cpr;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (row < G) v = *reinterpret_cast<const uint4*>(Yb + row * ystride + c * 8);
-    *reinterpret_cast<uint4*>(yimg + row * d + ((c ^ (row & 7)) << 3)) = v;
+  // ---- mask bytes (and the backward's rowsum gradients): loaded once, unconditionally, from clamped indices, ahead of the images.
+  //      Without a mask the bytes come from Y (never used): no load of this kernel sits under a branch ----
+  const bool has_mask = a.gmask != nullptr;
+  const unsigned char* gm = has_mask ? a.gmask + (long)b * G : reinterpret_cast<const unsigned char*>(a.Y);
+  unsigned char msc[GB], msm[GB];                                  // keys of the score epilogue (64 kb + 16 w + x) / of the softmax (64 kb + lane)
+#pragma unroll
+  for (int kb = 0; kb < GB; ++kb) {
+    msc[kb] = gm[min(64 * kb + 16 * w + x, G - 1)];
+    msm[kb] = BWD ? gm[min(64 * kb + lane, G - 1)] : (unsigned char)1;
   }
-  for (int idx = tid; idx < QROWS * cpr; idx += 256) {
-    const int row = idx / cpr, c = idx - row * cpr;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (row < h) v = *reinterpret_cast<const uint4*>(a.q2f + qoff + (long)row * d + c * 8);
-    else if (BWD && row >= 8 && row < 8 + h) v = *reinterpret_cast<const uint4*>(a.dPY + qoff + (long)(row - 8) * d + c * 8);
-    *reinterpret_cast<uint4*>(qg + row * d + ((c ^ (row & 7)) << 3)) = v;
+  float drs0 = 0.f, drs1 = 0.f;                                    // d_rowsum of this wave's heads 2w, 2w + 1
+  if constexpr (BWD) {
+    const float* dr = a.d_rowsum ? a.d_rowsum + ((long)b * Lq + i) * h : reinterpret_cast<const float*>(a.Y);
+    drs0 = dr[min(2 * w, h - 1)];
+    drs1 = dr[min(2 * w + 1, h - 1)];
+  }
+  // ---- stage the images ---------------------------------------------------------------------------------
+  switch (d >> 7) {
+    case 1: st2_stage<GP, QROWS, 1>(yimg, qg, Yb, ystride, a.q2f + qoff, BWD ? a.dPY + qoff : a.q2f + qoff, G, h, tid); break;
+    case 2: st2_stage<GP, QROWS, 2>(yimg, qg, Yb, ystride, a.q2f + qoff, BWD ? a.dPY + qoff : a.q2f + qoff, G, h, tid); break;
+    case 3: st2_stage<GP, QROWS, 3>(yimg, qg, Yb, ystride, a.q2f + qoff, BWD ? a.dPY + qoff : a.q2f + qoff, G, h, tid); break;
+    default: st2_stage<GP, QROWS, 4>(yimg, qg, Yb, ystride, a.q2f + qoff, BWD ? a.dPY + qoff : a.q2f + qoff, G, h, tid); break;
   }
   for (int idx = tid; idx < 16 * GP / 8; idx += 256) reinterpret_cast<uint4*>(pimg)[idx] = make_uint4(0, 0, 0, 0);
   __syncthreads();
@@ -613,7 +664,7 @@ __global__ __launch_bounds__(256) void st2_mfma_kernel(const St2Args a) {
         const int hh = lg * 4 + r;
         float s = acc[r];
         if (g >= G) s = -INFINITY;
-        else if (a.gmask && a.gmask[(long)b * G + g] == 0) s = MASK_FILL;
+        else if (has_mask && msc[kb] == 0) s = MASK_FILL;
         scf[hh * GP + g] = s;
         if constexpr (BWD) dpf[hh * GP + g] = acd[r];
       }
@@ -650,8 +701,14 @@ __global__ __launch_bounds__(256) void st2_mfma_kernel(const St2Args a) {
           rs += p * m[kb];
         } else {
           dp[kb] = g < G ? dpf[hh * GP + g] : 0.f;
-          if (a.d_rowsum && g < G) dp[kb] += a.d_rowsum[((long)b * Lq + i) * h + hh];
-          dp[kb] *= m[kb];                                    // dP = mask/(1-p) * dP'
+          if (a.d_rowsum && g < G) dp[kb] += (hh & 1) ? drs1 : drs0;
+          // dP = mask/(1-p) * dP', rounded on its own.  With every load out of the way this product and the later dP - dot share
+          // a basic block and the compiler would fuse them into one fma: another rounding than the 64-row form and earlier
+          // builds whenever dropout is on (m != 1).  Without the contract flag on the product it cannot be fused.
+          {
+#pragma clang fp contract(off)
+            dp[kb] *= m[kb];
+          }
           dot += p * dp[kb];
         }
       }
@@ -665,8 +722,9 @@ __global__ __launch_bounds__(256) void st2_mfma_kernel(const St2Args a) {
 #pragma unroll
         for (int kb = 0; kb < GB; ++kb) {
           const int g = 64 * kb + lane;
+          if (g >= GP) continue;                              // (HALF: lanes 32-63 hold no key)
           float ds = e[kb] * (dp[kb] - dot);
-          if (g >= G || (a.gmask && a.gmask[(long)b * G + g] == 0)) ds = 0.f;
+          if (g >= G || (has_mask && msm[kb] == 0)) ds = 0.f;
           pimg[hh * GP + g] = (bf16_t)ds;
           pimg[(8 + hh) * GP + g] = (bf16_t)(e[kb] * m[kb]);
         }
@@ -704,7 +762,7 @@ __global__ __launch_bounds__(256) void st2_mfma_kernel(const St2Args a) {
       const int col0 = (w * nf + f) * 16;
       const uint4 bfr = k16_only(sfrag_cols(qg, d, col0, 0, lane16), lane);
 #pragma unroll
-      for (int mi = 0; mi < 4 * GB; ++mi) {
+      for (int mi = 0; mi < GP / 16; ++mi) {
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
         acc = mfma_bf16(k16_only(frag_cols(pimg, GP, mi * 16, 0, lane16), lane), bfr, acc);
 #pragma unroll
@@ -725,13 +783,6 @@ __global__ __launch_bounds__(256) void st2_mfma_kernel(const St2Args a) {
 //   S = Q K^T, dP = dO V^T (+ dP_ext) -> softmax / softmax-backward in the accumulator layout
 //   dQ = scale dS K,  dK = scale dS^T Q,  dV = P^T dO
 // =====================================================================================================
-// v or zeros, component-wise (a ternary on the uint4 struct turns into an address select through scratch memory)
-__device__ __forceinline__ uint4 keep4(uint4 v, bool keep) {
-  const unsigned m = keep ? 0xffffffffu : 0u;
-  v.x &= m; v.y &= m; v.z &= m; v.w &= m;
-  return v;
-}
-
 struct MhaBwdArgs {
   const bf16_t *Q, *K, *V, *dO; const unsigned char* mask; const float* dPext;
   bf16_t *dQ, *dK, *dV;
@@ -951,7 +1002,10 @@ int bist_st2_mfma(const void* q2f, const void* Y, const unsigned char* gmask, vo
   if (G > 128 || h > 8 || d > 512 || (d % 128) != 0) return 0;
   if (((uintptr_t)q2f | (uintptr_t)Y | (uintptr_t)(bwd ? dPY : q2f)) % 16) return 0;
   static const int no_half = [] { const char* e = getenv("BIST_ST2_NO_HALF"); return e ? atoi(e) : 0; }();      // tuning aid
-  const bool half = !bwd && G <= 32 && !no_half;
+  // tuning aid: 1 = the backward keeps its 64-row images at G <= 32.  Read at every BACKWARD launch (not once, like its neighbour) for one
+  // reason: the test that compares both forms bit for bit toggles it inside one process; set it before the process starts otherwise
+  const char* bwd_full = bwd && G <= 32 ? getenv("BIST_ST2_BWD_FULL") : nullptr;
+  const bool half = G <= 32 && (bwd ? !(bwd_full && atoi(bwd_full)) : !no_half);
   const int gb = G > 64 ? 2 : 1, gp = half ? 32 : 64 * gb;
   const size_t lds = (size_t)gp * d * 2 + (size_t)(bwd ? 16 : 8) * d * 2 + (size_t)(bwd ? 2 : 1) * 8 * gp * 4 + 16 * gp * 2;
   St2Args a{(const bf16_t*)q2f, (const bf16_t*)Y, gmask, (bf16_t*)PY, (const bf16_t*)dPY, (bf16_t*)dq2f, (bf16_t*)dY, G, Lq, h, d,
@@ -962,7 +1016,10 @@ int bist_st2_mfma(const void* q2f, const void* Y, const unsigned char* gmask, vo
     BIST_LDS_OPTIN((&st2_mfma_kernel<BWD_, GB_>), 160 * 1024, "bist_st_stage2 (matrix-core kernel)", -1);                  \
     hipLaunchKernelGGL((st2_mfma_kernel<BWD_, GB_>), grid, dim3(256), lds, st, a);                                         \
   } while (0)
-  if (bwd) { if (gb == 2) ST2_GO(true, 2); else ST2_GO(true, 1); }
+  if (bwd && half) {
+    BIST_LDS_OPTIN((&st2_mfma_kernel<true, 1, true>), 160 * 1024, "bist_st_stage2 (matrix-core kernel)", -1);
+    hipLaunchKernelGGL((st2_mfma_kernel<true, 1, true>), grid, dim3(256), lds, st, a);
+  } else if (bwd) { if (gb == 2) ST2_GO(true, 2); else ST2_GO(true, 1); }
   else if (half) {
     BIST_LDS_OPTIN((&st2_mfma_kernel<false, 1, true>), 160 * 1024, "bist_st_stage2 (matrix-core kernel)", -1);
     hipLaunchKernelGGL((st2_mfma_kernel<false, 1, true>), grid, dim3(256), lds, st, a);

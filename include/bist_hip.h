@@ -58,7 +58,8 @@ int bist_device_ok(void);
 #define BIST_K_DECSTACK 10      /* bist_decoder_stack_fwd (persistent decoder-stack kernel)                   */
 #define BIST_K_ST1_FUSED_TRAIN 11   /* bist_st_stage1_fused_train_fwd                                        */
 #define BIST_K_ST1_PBWD 12      /* bist_st_stage1_pv_bwd_p (backward core fed with the saved probabilities)  */
-#define BIST_K_COUNT 13
+#define BIST_K_MHA_FWD_DK64 13  /* of the BIST_K_MHA_FWD launches, those of mha_core_dk64_kernel (operands fetched ahead) */
+#define BIST_K_COUNT 14
 int64_t bist_launch_count(int32_t family);
 void bist_launch_count_reset(void);
 /* Development hook: hand the fused stage-1 kernel (which = 0) or the persistent decoder kernel (which = 1) a caller-owned DEVICE
