@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libbist_hip.so")
 
 F32, BF16 = 0, 1
 GRAD_SUMSQ_MAX_SLOTS = 4096      # BIST_GRAD_SUMSQ_MAX_SLOTS (include/bist_hip.h)
+STATE_MAX_SLOTS = 4096           # BIST_STATE_MAX_SLOTS (include/bist_hip.h)
 ACT_NONE, ACT_RELU, ACT_GATE = 0, 1, 2
 # kernel families of bist_launch_count (include/bist_hip.h: BIST_K_*)
 K_ST1_MFMA_FWD, K_ST1_MFMA_BWD, K_ST1_VALU, K_ST2_MFMA_FWD, K_ST2_MFMA_BWD, K_ST2_VALU, K_MHA_FWD, K_MHA_BWD_MFMA, K_MHA_BWD_VALU, K_ST1_FUSED, K_DECSTACK, K_ST1_FUSED_TRAIN, K_ST1_PBWD, K_MHA_FWD_DK64 = range(14)
@@ -201,6 +202,7 @@ SIGNATURES = {
     "bist_clip_hyper": (C.c_int, [_P, _I32, _F, _P, _P, _P, _P]),
     "bist_adam_step_dev_guard": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _F, _F, _F, _I32, _I32, _I32, _P]),
     "bist_adam_accum_dev_guard": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _F, _F, _F, _I32, _I32, _I32, _P]),
+    "bist_state_copy": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I64, _P, _I32, _I32, _P]),
     "bist_cast": (C.c_int, [_P, _P, _I64, _I32, _I32, _P]),
     "bist_graph_capture_tail": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "bist_graph_nodes": (C.c_int, [_P, C.POINTER(C.c_void_p), _I32, C.POINTER(C.c_int32)]),

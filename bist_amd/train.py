@@ -41,6 +41,7 @@ from .model.label_smoothing import LabelSmoothing
 from .model.modules import MultiHeadedAttention
 from .model.optimize import SimpleLossCompute
 from . import functional as Fn
+from . import checkpoint as CK
 from . import graphsplit as GS
 from . import stamps as STM
 from . import ops, parallel
@@ -372,6 +373,7 @@ class Trainer:
                 pk[idx] = (w, b)
             m._pk = pk
         self.params = order
+        self._layout = [(names[id(p)], offs[id(p)], p.numel(), tuple(p.shape)) for p in order]      # checkpoints: (name, offset, numel, shape) in flat order
         # device-side step counter mixed into every dropout seed, so that a captured graph draws new masks
         # weight-gradient GEMMs on their own stream (autograd._WeightGradStream): measured SLOWER in a replayed hipGraph
         # (21.2 vs 18.3 ms/step, round 1: ~300 extra cross-stream edges cost more than the overlap gains), so opt-in
@@ -1234,6 +1236,133 @@ class Trainer:
         if side is not None:
             main.wait_stream(side)
         return {k: v.detach() for k, v in terms.items()}
+
+    # ---- checkpoints: device snapshot, rollback, save and resume (bist_amd/checkpoint.py) ----------------
+    def _need_device(self, what: str) -> None:
+        if not self.master.is_cuda:
+            raise RuntimeError("Trainer.%s: the copy and its digests are a device launch (bist_state_copy); a trainer on %s cannot "
+                               "take or restore a snapshot" % (what, self.master.device))
+
+    def snapshot(self, into: Optional["CK.TrainerSnapshot"] = None) -> "CK.TrainerSnapshot":
+        """The optimiser state as it is between two steps, copied on the device: ONE bist_state_copy of master / m / v into the
+        snapshot's buffers (with the digests of what it copied) and stream-ordered copies of the device scalars, on the current stream;
+        the host counters and the dropout seed state are read now.  No host synchronisation.  into: a previous snapshot of this size
+        whose buffers are reused ("best so far" after every evaluate()).  The gradient buffer is not state."""
+        self._need_device("snapshot")
+        self.flush()
+        snap = into
+        if snap is None:
+            snap = CK.TrainerSnapshot(self.numel, self.master.device, self.clip)
+        elif snap.numel != self.numel or snap.master.device != self.master.device:
+            raise ValueError("Trainer.snapshot(into=...): a snapshot of %d elements on %s cannot hold this trainer's %d on %s"
+                             % (snap.numel, snap.master.device, self.numel, self.master.device))
+        CK.state_copy((self.master, self.m, self.v), snap.tensors(), None, snap.digests)
+        snap.hyper.copy_(self.hyper)
+        if self.clip:
+            if snap.skipped is None:
+                snap.skipped = torch.zeros(1, device=self.master.device, dtype=torch.int64)
+            snap.skipped.copy_(self.skipped)
+        elif snap.skipped is not None:
+            snap.skipped.zero_()
+        snap.step, snap.passes = self._step, (self._passes if self.accumulate else self._step)
+        snap.seed = (Fn._SEED[0], Fn._SEED[1])
+        snap.layout, snap.config = CK.describe(self)
+        snap.event = torch.cuda.Event()
+        snap.event.record()
+        return snap
+
+    def restore(self, snap: "CK.TrainerSnapshot") -> None:
+        """Back to a snapshot: ONE bist_state_copy into the live buffers that also rewrites the compute-dtype weights with Adam's cast,
+        then the scalars a step does not derive itself (hyper[5:8], skipped), the counters and the dropout seed state.  Every buffer keeps
+        its address: captured steps and evaluation graphs stay valid.  No host synchronisation, except on a trainer that exchanges
+        gradients during the backward pass (its bucket flags carry step numbers: the device is drained and the flags are cleared)."""
+        self._need_device("restore")
+        if snap.numel != self.numel or snap.master.device != self.master.device:
+            raise ValueError("Trainer.restore: a snapshot of %d elements on %s does not fit this trainer's %d on %s"
+                             % (snap.numel, snap.master.device, self.numel, self.master.device))
+        if self.overlap and snap.world != self.world:
+            raise ValueError("Trainer.restore: the snapshot was taken with world %d, this trainer exchanges gradients over %d ranks"
+                             % (snap.world, self.world))
+        if snap.event is not None:
+            torch.cuda.current_stream().wait_event(snap.event)
+        work = None if self.compute_dtype == torch.float32 else self.flat_param
+        CK.state_copy(snap.tensors(), (self.master, self.m, self.v), work, self._state_digests())
+        self.hyper[5:8].copy_(snap.hyper[5:8])         # (hyper[0:5] belong to the head of the step)
+        if self.clip:
+            if snap.skipped is not None:
+                self.skipped.copy_(snap.skipped)
+            else:
+                self.skipped.zero_()
+        self.pending.zero_()
+        self._pending_host = False
+        self._step = int(snap.step)
+        if self.accumulate:
+            self._passes = int(snap.passes)
+        Fn._SEED[0], Fn._SEED[1] = int(snap.seed[0]), int(snap.seed[1])
+        ops.WEIGHTS_EPOCH += 1                         # the evaluation and decode graphs' derived operands are keyed by it
+        if self.overlap:
+            # _await_bucket tests flags < _step: after going back in time the flags of the later steps would pass at once
+            torch.cuda.synchronize()
+            self._flags.zero_()
+
+    def _state_digests(self) -> torch.Tensor:
+        """The trainer's own digest slots, for launches whose digests nobody keeps (restore) or reads at once (state_digest, load)."""
+        if getattr(self, "_ckpt_digests", None) is None:
+            self._ckpt_digests = torch.zeros(3, CK.SLOTS, device=self.master.device, dtype=torch.int64)
+        return self._ckpt_digests
+
+    def state_digest(self) -> Dict[str, int]:
+        """Synchronises: the 64-bit digests of the live master / m / v (include/bist_hip.h: bist_state_copy) from a digest-only launch --
+        what two ranks, or a trainer and a file, compare instead of the buffers."""
+        self._need_device("state_digest")
+        self.flush()
+        CK.state_copy((self.master, self.m, self.v), None, None, self._state_digests())
+        return CK.digest_totals(self._state_digests())
+
+    def state_dict(self) -> Dict[str, object]:
+        """snapshot().state_dict(): the optimiser state as CPU data (synchronises)."""
+        return self.snapshot().state_dict()
+
+    def load_state_dict(self, sd, strict: bool = True) -> None:
+        """Validate on the host (ValueError naming the field, before any launch), upload into a device snapshot, compare the digests
+        of what arrived with the checkpoint's (a mismatch raises ValueError and leaves the trainer untouched), restore.  Any
+        compute_dtype loads: master is fp32 and the restore casts.  strict=False keeps this trainer's d_model, warmup, factor, betas, eps."""
+        CK.validate(sd, self, strict)
+        self._need_device("load_state_dict")
+        if self.overlap and int(sd["config"]["world"]) != self.world:
+            raise ValueError("Trainer.load_state_dict: config.world is %r, this trainer exchanges gradients over %d ranks"
+                             % (sd["config"]["world"], self.world))
+        snap = CK.upload(sd, self)
+        CK.state_copy(snap.tensors(), None, None, snap.digests)
+        got = CK.digest_totals(snap.digests)
+        for k in ("master", "m", "v"):
+            if got[k] != sd["digest"][k]:
+                raise ValueError("Trainer.load_state_dict: digest of %s is %016x on the device, the checkpoint says %016x"
+                                 % (k, got[k], sd["digest"][k]))
+        self.restore(snap)
+
+    def save(self, path) -> None:
+        """state_dict() written with torch.save to path + ".tmp", then moved into place (os.replace)."""
+        path = os.fspath(path)
+        torch.save(self.state_dict(), path + ".tmp")
+        os.replace(path + ".tmp", path)
+
+    def load(self, path) -> None:
+        self.load_state_dict(torch.load(os.fspath(path), map_location="cpu", weights_only=True))
+
+    def master_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The model's state_dict keys -> fp32 views of ``master`` (a buffer that is no parameter: the model's own tensor): the lossless
+        export -- in bf16 the model's parameters are the rounded copy."""
+        self.flush()
+        where = {id(p): (o, k) for p, (_n, o, k, _s) in zip(self.params, self._layout)}
+        out = {}
+        for key, t in self.model.state_dict(keep_vars=True).items():
+            if id(t) in where:
+                o, k = where[id(t)]
+                out[key] = self.master[o:o + k].view(t.shape)
+            else:
+                out[key] = t.detach()
+        return out
 
 
 def run_epoch(data, loader, vocab, epoch, model, loss_compute, eval=False, gen_valid_indices=None, report=None):

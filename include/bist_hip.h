@@ -720,6 +720,32 @@ int bist_noam_hyper_pending(int64_t* pending, float* hyper, float d_model, float
 int bist_adam_apply_dev(float* p, void* g, float* m, float* v, void* work, int64_t n, const float* hyper, float beta1,
                         float beta2, float eps, int32_t grad_dtype, int32_t work_dtype, void* stream);
 
+/* Trainer checkpoints: the optimiser state -- three flat fp32 ranges of n elements: master weights p, Adam moments
+ * m and v -- copied and digested in ONE pass with 16-byte accesses.  The reference writes its model after validation and keeps the best
+ * one (train.py:156-177).  Three uses of one launch:
+ *   snapshot     dst_* = the snapshot's buffers, work = NULL
+ *   restore      src_* = the snapshot's buffers, dst_* = the live ones, work = the compute-dtype copy of the weights: work[i] =
+ *                cast(src_p[i]), the cast of bist_adam_step_dev (a plain copy for BIST_F32), so work holds the bits Adam would have written
+ *   digest only  dst_p = dst_m = dst_v = NULL: nothing but the digests is written (and work, if given)
+ * The dst pointers are given together or not at all; no src may be a dst; src, dst and a BIST_F32 work are 16-byte aligned, a BIST_BF16
+ * work 8-byte; n >= 1 (a tail below 4 elements takes a scalar form).
+ *
+ * digests[t * nslots + s], t = 0 (p), 1 (m), 2 (v): slot s covers the chunk [s * c, min(n, (s + 1) * c)), c = ceil(n / nslots) rounded
+ * up to a multiple of 8 elements -- a function of (n, nslots) alone.  Every slot is written by every launch (no memset), an empty chunk
+ * writes 0.  max_blocks > 0: at most that many workgroups walk the slots; 0: one workgroup per slot.  No atomics, no tickets.
+ *
+ * The digest of a tensor x of n fp32 elements, which a host can recompute:
+ *   w_j = bits(x[2j - 2]) | bits(x[2j - 1]) << 32      j = 1 .. ceil(n / 2): x read as little-endian 64-bit words, counted from 1
+ *                                                      through the WHOLE tensor; n odd: the high half of the last word is 0
+ *   h_j = mix(w_j + j * 0x9E3779B97F4A7C15)            mix (the finaliser of splitmix64): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                                                      z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31      (all modulo 2^64)
+ *   a slot = the sum modulo 2^64 of the h_j of its words; the tensor's digest = the sum modulo 2^64 of its slots.
+ * Integer addition: the digest does not depend on nslots, max_blocks, the grid or the order of arrival; the j term makes it depend on
+ * where a word stands.  1 <= nslots <= BIST_STATE_MAX_SLOTS.                                                                        */
+#define BIST_STATE_MAX_SLOTS 4096
+int bist_state_copy(const float* src_p, const float* src_m, const float* src_v, float* dst_p, float* dst_m, float* dst_v,
+                    void* work, int32_t work_dtype, int64_t n, uint64_t* digests, int32_t nslots, int32_t max_blocks, void* stream);
+
 /* dst = cast(src) between f32 and bf16 (n elements). */
 int bist_cast(const void* src, void* dst, int64_t n, int32_t src_dtype, int32_t dst_dtype, void* stream);
 
