@@ -184,6 +184,7 @@ SIGNATURES = {
     "bist_decoder_cache_fill": (C.c_int, [_P, _I32, _I32, _P]),
     "bist_stage_inputs": (C.c_int, [_P, _I32, _P]),
     "bist_stage_train_batch": (C.c_int, [C.POINTER(BistTrainStage), _P]),
+    "bist_stage_audio": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "bist_eval_accumulate": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I32, C.POINTER(C.c_void_p), _I32, _P, _P, _P]),
     "bist_xent_smooth_fwd": (C.c_int, [_P, _P, _I64, _I64, _I32, _F, _I32, _P, _P, _P]),
     "bist_xent_smooth_bwd": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _I32, _P, _P, _I32, _I32, _F, _I32, _P]),

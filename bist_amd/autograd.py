@@ -620,7 +620,7 @@ class FuseDynFn(Function):
         p2 = [p.reshape(-1, d) for p in parts]
         p2 = [p if p.is_contiguous() else p.contiguous() for p in p2]
         n_, ns_ = len(p2), W.shape[0]
-        one = (FUSE_ONE_LAUNCH and 1 <= n_ <= 4 and ns_ <= 4 and d % 8 == 0 and W.stride(1) == 1 and W.stride(0) % 8 == 0 and W.data_ptr() % 16 == 0
+        one = (FUSE_ONE_LAUNCH and 1 <= n_ <= 5 and ns_ <= 4 and d % 8 == 0 and W.stride(1) == 1 and W.stride(0) % 8 == 0 and W.data_ptr() % 16 == 0
                and W.dtype in (torch.bfloat16, torch.float32) and all(p.dtype == W.dtype and p.data_ptr() % 16 == 0 for p in p2)
                and (bias is None or bias.dtype == W.dtype))
         if one:                                          # the fusion logits as ONE launch over the un-concatenated parts (bist_switch_logits_fwd)
@@ -630,7 +630,7 @@ class FuseDynFn(Function):
                                              dtype_code(W.dtype), _stream()), "bist_switch_logits_fwd")
         else:
             score = None
-            for j, pj in enumerate(p2):                  # concat order of the reference: query, cap, spatial, temporal
+            for j, pj in enumerate(p2):                  # concat order of the reference: query, cap, spatial, temporal, audio
                 score = ops.linear(pj, W[:, j * d:(j + 1) * d], bias if j == 0 else None, out=score, accumulate=j > 0)
         ctx.one = one
         xs = [p2[k] for k in xs_idx]
@@ -1194,7 +1194,7 @@ class XentSmoothLossFn(Function):
 
 class SwitchLogitsFn(Function):
     """lin(cat(parts, -1)) of the pointer generators' switch (generator.py:69-71, 119-121) without the concatenation: one launch forward,
-    two backward (bist_switch_logits_fwd / _bwd); parts: n <= 4 tensors [rows, d]; returns f32 [rows, ns].  Under the trainer the weight
+    two backward (bist_switch_logits_fwd / _bwd); parts: n <= 5 tensors [rows, d]; returns f32 [rows, ns].  Under the trainer the weight
     gradient accumulates into the flat gradient view and the bias gradient into its fp32 accumulator, like LinearFn."""
 
     @staticmethod

@@ -103,11 +103,14 @@ __global__ __launch_bounds__(256) void text_vector_kernel(const float* __restric
   *reinterpret_cast<uint4*>(out + row * d + c0) = *reinterpret_cast<const uint4*>(o);
 }
 
-// The switch logits of (Multi)PointerGenerator (generator.py:71, 119-121): pointer_gen_W applied to the concatenation of n_parts <= 4
+// The switch logits of (Multi)PointerGenerator (generator.py:71, 119-121): pointer_gen_W applied to the concatenation of n_parts <= 5
 // [rows, d] tensors WITHOUT the concatenation -- part j multiplies column block j of W [ns <= 4][n_parts d].  One launch forward (a wave
 // per row) and two backward (the parts' gradients: a wave per row; the weight / bias gradient: a workgroup per part and 64 four-byte column
 // pieces, sixteen row slices per workgroup) where a product per part took 4 launches forward and 12 backward (cast + dX + dW each).
-struct SwParts { const void* x[4]; void* dx[4]; const void* res[4]; int n; };
+// (five parts: the modality fusion with audio, decoder.py:148-154 -- query, cap, spatial, temporal, audio -> four logits; every kernel walks
+// the parts it is given in order, so a call with <= 4 parts runs the arithmetic it always ran)
+constexpr int SW_MAX_PARTS = 5;
+struct SwParts { const void* x[SW_MAX_PARTS]; void* dx[SW_MAX_PARTS]; const void* res[SW_MAX_PARTS]; int n; };
 
 template <typename T, typename TO>
 __global__ __launch_bounds__(256) void switch_logits_fwd_kernel(SwParts a, const T* __restrict__ W, long ldw, const T* __restrict__ bias,
@@ -675,9 +678,9 @@ extern "C" int bist_pointer_mix_fwd(const float* logits, const float* switch_log
 }
 
 static int sw_parts(SwParts& a, const void* const* parts, void* const* dparts, const void* const* residuals, int32_t n_parts, const char* who) {
-  BIST_REQUIRE(parts && n_parts >= 1 && n_parts <= 4, "%s: 1..4 parts", who);
+  BIST_REQUIRE(parts && n_parts >= 1 && n_parts <= SW_MAX_PARTS, "%s: 1..5 parts", who);
   a.n = n_parts;
-  for (int j = 0; j < 4; ++j) { a.x[j] = nullptr; a.dx[j] = nullptr; a.res[j] = nullptr; }
+  for (int j = 0; j < SW_MAX_PARTS; ++j) { a.x[j] = nullptr; a.dx[j] = nullptr; a.res[j] = nullptr; }
   for (int j = 0; j < n_parts; ++j) {
     BIST_REQUIRE(parts[j] && ((uintptr_t)parts[j] & 15) == 0 && (!dparts || ((uintptr_t)dparts[j] & 15) == 0) && (!residuals || ((uintptr_t)residuals[j] & 15) == 0),
                  "%s: part %d null or not 16-byte aligned", who, j);

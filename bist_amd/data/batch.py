@@ -24,10 +24,11 @@ def subsequent_mask(size: int, device=None) -> torch.Tensor:
 class Batch:
     """Same attribute names as the reference Batch (dataset.py:59-99).
 
-    query/his/cap/trg/trg_y: int64 [B, L*]; fts: float [B,T,S,C] (f32 or bf16).
+    query/his/cap/trg/trg_y: int64 [B, L*]; fts: float [B,T,S,C] (f32 or bf16); audio_fts: as the reference passes it -- None, or a
+    list holding one [B,Ta,Da] array (numpy or tensor; a bare tensor is accepted too) -- dataset.py:60, 83-87.
     """
 
-    def __init__(self, query, his, fts, cap, trg, trg_y=None, pad: int = PAD, vids=None, qa_ids=None):
+    def __init__(self, query, his, fts, cap, trg, trg_y=None, pad: int = PAD, vids=None, qa_ids=None, audio_fts=None):
         self.vids, self.qa_ids = vids, qa_ids
         self.query, self.his, self.cap, self.trg, self.trg_y = query, his, cap, trg, trg_y
         self.fts = fts
@@ -40,10 +41,12 @@ class Batch:
         self.trg_mean_mask = (trg_y != pad) if trg_y is not None else None
         self.ntokens = (trg_y != pad).sum() if trg_y is not None else None   # dataset.py:98
         self.qntokens = (query != pad).sum()                        # dataset.py:99
-        self.audio_fts = None
+        self.audio_fts = _audio_tensor(audio_fts)                   # dataset.py:83-86
         self.audio_mask = None
         if fts is not None:
             self._derive_temporal_mask()
+        if self.audio_fts is not None:
+            self._derive_audio_mask()
 
     def _derive_temporal_mask(self):
         if self.fts.is_cuda:
@@ -51,6 +54,14 @@ class Batch:
             self.temporal_mask = ops.temporal_mask(self.fts)
         else:   # host-side batches (before move_to_cuda) follow the reference expression literally
             self.temporal_mask = (self.fts.sum(2).sum(-1) != 0).unsqueeze(-2)
+
+    def _derive_audio_mask(self):
+        """audio_mask = (audio_fts.sum(-1) != 0).unsqueeze(-2) (dataset.py:87): the SUM of a row, so a row whose entries cancel is masked."""
+        if self.audio_fts.is_cuda:
+            from .. import ops
+            self.audio_mask = ops.audio_mask(self.audio_fts)
+        else:
+            self.audio_mask = (self.audio_fts.sum(-1) != 0).unsqueeze(-2)
 
     @staticmethod
     def make_std_mask(tgt, pad):
@@ -60,11 +71,26 @@ class Batch:
     def move_to_cuda(self):
         """dataset.py:107-127."""
         for name in ("query", "his", "cap", "trg", "trg_y", "query_mask", "query_mask2", "his_mask", "cap_mask", "trg_mask",
-                     "trg_mean_mask", "fts", "temporal_mask"):
+                     "trg_mean_mask", "fts", "temporal_mask", "audio_fts", "audio_mask"):
             v = getattr(self, name)
             if v is not None:
                 setattr(self, name, v.to("cuda", non_blocking=True))
         return self
+
+
+def _audio_tensor(audio_fts):
+    """The reference's audio argument -- None, an empty list, or a list holding one [B,Ta,Da] array (dataset.py:85-86) -- as a tensor."""
+    if audio_fts is None:
+        return None
+    if isinstance(audio_fts, (list, tuple)):
+        if len(audio_fts) == 0:
+            return None
+        audio_fts = audio_fts[0]
+    if not torch.is_tensor(audio_fts):
+        audio_fts = torch.from_numpy(audio_fts).float()
+    if audio_fts.dim() != 3:
+        raise ValueError("audio_fts must be [B, Ta, Da]")
+    return audio_fts
 
 
 _DERIVED = ("query_mask", "query_mask2", "his_mask", "cap_mask", "trg_mask", "trg_mean_mask", "temporal_mask")
@@ -76,21 +102,22 @@ class SourceBatch(Batch):
     the class lengths.  A batch handed to it this way costs two token counts instead of ten mask launches and a pass of
     bist_temporal_mask over the features, so a fed class step reads the features once.  Any other consumer sees a complete Batch."""
 
-    def __init__(self, query, his, fts, cap, trg, trg_y=None, pad: int = PAD, vids=None, qa_ids=None):
+    def __init__(self, query, his, fts, cap, trg, trg_y=None, pad: int = PAD, vids=None, qa_ids=None, audio_fts=None):
         self.vids, self.qa_ids = vids, qa_ids
         self.query, self.his, self.cap, self.trg, self.trg_y = query, his, cap, trg, trg_y
         self.fts = fts
         self.pad = pad
         self.ntokens = (trg_y != pad).sum() if trg_y is not None else None   # dataset.py:98
         self.qntokens = (query != pad).sum()                                  # dataset.py:99
-        self.audio_fts = None
-        self.audio_mask = None
+        self.audio_fts = _audio_tensor(audio_fts)
+        if self.audio_fts is None:
+            self.audio_mask = None                                            # (with audio: derived on first access, like the other masks)
 
     def __getattr__(self, name):
         # (called only for attributes not set yet: the derived fields, all at once, from the fields as they are now)
-        if name not in _DERIVED or "query" not in self.__dict__:
+        if (name not in _DERIVED and name != "audio_mask") or "query" not in self.__dict__:
             raise AttributeError(name)
-        full = Batch(self.query, self.his, self.fts, self.cap, self.trg, self.trg_y, pad=self.pad)
-        for f in _DERIVED:
+        full = Batch(self.query, self.his, self.fts, self.cap, self.trg, self.trg_y, pad=self.pad, audio_fts=self.audio_fts)
+        for f in _DERIVED + (("audio_mask",) if self.audio_fts is not None else ()):
             self.__dict__.setdefault(f, getattr(full, f))
         return self.__dict__[name]

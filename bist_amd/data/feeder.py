@@ -39,16 +39,18 @@ import torch
 
 from .._lib import check, lib
 from ..ops import dtype_code
-from .batch import PAD, Batch, SourceBatch
+from .batch import PAD, Batch, SourceBatch, _audio_tensor
 
 _FIELDS = ("query", "his", "cap", "trg", "trg_y")
 
 
 class HostBatch:
-    """What a collate function hands over: CPU tensors (ids int64, features fp32 or bf16 ``[B,T,S,C]``)."""
+    """What a collate function hands over: CPU tensors (ids int64, features fp32 or bf16 ``[B,T,S,C]``; audio features
+    ``[B,Ta,Da]`` -- or, as the reference passes them, a list holding that one array -- or None)."""
 
-    def __init__(self, query, his, fts, cap, trg, trg_y=None):
+    def __init__(self, query, his, fts, cap, trg, trg_y=None, audio_fts=None):
         self.query, self.his, self.fts, self.cap, self.trg, self.trg_y = query, his, fts, cap, trg, trg_y
+        self.audio_fts = _audio_tensor(audio_fts)
 
 
 SLOTS = max(2, int(__import__("os").environ.get("BIST_FEEDER_SLOTS", "3")))      # device / pinned staging slots (2: the round-3 double buffer)
@@ -128,8 +130,8 @@ class DeviceFeeder:
             # pinned staging buffers were read by copies that _finish() has waited for.)
             self._free[slot].synchronize()
         with torch.cuda.stream(self.copy_stream):
-            for name in _FIELDS + ("fts",):
-                t = getattr(hb, name)
+            for name in _FIELDS + ("fts", "audio_fts"):       # (the audio features travel in the slot like the video features)
+                t = getattr(hb, name, None)
                 if t is None:
                     out[name] = None
                     continue
@@ -151,12 +153,13 @@ class DeviceFeeder:
         self.copy_stream.synchronize()
         self._in_flight = False
         dev = self._dev[slot]
-        d = tensors["fts"]
-        if d is not None and d.dtype != self.feature_dtype and self.length_classes is None:
-            c = self._slot(dev, "fts_cast", d, self.feature_dtype, False)
-            check(lib.bist_cast(d.data_ptr(), c.data_ptr(), d.numel(), dtype_code(d.dtype), dtype_code(self.feature_dtype),
-                                torch.cuda.current_stream(self.device).cuda_stream), "bist_cast")
-            tensors["fts"] = c
+        for name in ("fts", "audio_fts"):
+            d = tensors.get(name)
+            if d is not None and d.dtype != self.feature_dtype and self.length_classes is None:
+                c = self._slot(dev, name + "_cast", d, self.feature_dtype, False)
+                check(lib.bist_cast(d.data_ptr(), c.data_ptr(), d.numel(), dtype_code(d.dtype), dtype_code(self.feature_dtype),
+                                    torch.cuda.current_stream(self.device).cuda_stream), "bist_cast")
+                tensors[name] = c
         for t in tensors.values():
             if t is not None:
                 t._bist_generation = getattr(t, "_bist_generation", 0) + 1      # the slot tensors are reused: tell consumers that cache by identity
@@ -175,8 +178,10 @@ class DeviceFeeder:
 
     def _batch(self, tensors) -> Batch:
         if self.length_classes is not None:      # masks on first access only: the class-mode Trainer derives its own (SourceBatch)
-            return SourceBatch(tensors["query"], tensors["his"], tensors["fts"], tensors["cap"], tensors["trg"], tensors["trg_y"], pad=self.pad)
-        return Batch(tensors["query"], tensors["his"], tensors["fts"], tensors["cap"], tensors["trg"], tensors["trg_y"], pad=self.pad)
+            return SourceBatch(tensors["query"], tensors["his"], tensors["fts"], tensors["cap"], tensors["trg"], tensors["trg_y"], pad=self.pad,
+                               audio_fts=tensors.get("audio_fts"))
+        return Batch(tensors["query"], tensors["his"], tensors["fts"], tensors["cap"], tensors["trg"], tensors["trg_y"], pad=self.pad,
+                     audio_fts=tensors.get("audio_fts"))
 
     # -- iteration -------------------------------------------------------------------------------
     def __iter__(self) -> Iterator[Batch]:

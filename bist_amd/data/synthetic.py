@@ -14,7 +14,9 @@ SOS, EOS = 2, 3
 
 def synthetic_batch(B: int, T: int = 32, S: int = 49, C: int = 2048, Lq: int = 20, Lh: int = 60, Lc: int = 25,
                     Lt: int = 20, vocab: int = 3000, seed: int = 1234, device="cuda", dtype=torch.bfloat16,
-                    ragged: bool = True) -> Batch:
+                    ragged: bool = True, audio=None) -> Batch:
+    """audio=(Ta, Da): N(0,1) audio features [B, Ta, Da] as well, with trailing all-zero rows on some clips (ragged audio lengths; drawn
+    after everything else, so the other fields equal those of the same call without audio)."""
     rs = np.random.RandomState(seed)
     fts = torch.from_numpy(rs.standard_normal((B, T, S, C)).astype(np.float32))
     if ragged:
@@ -41,4 +43,13 @@ def synthetic_batch(B: int, T: int = 32, S: int = 49, C: int = 2048, Lq: int = 2
                 trg[i, cut + 1:] = PAD
                 trg_y[i, cut - 1] = EOS
     dev = torch.device(device)
-    return Batch(query.to(dev), his.to(dev), fts.to(dev).to(dtype), cap.to(dev), trg.to(dev), trg_y.to(dev))
+    au = None
+    if audio is not None:
+        Ta, Da = audio
+        au = torch.from_numpy(rs.standard_normal((B, Ta, Da)).astype(np.float32))
+        if ragged:
+            for i in range(B):
+                if rs.rand() < 0.5 and Ta > 1:
+                    au[i, int(rs.randint((Ta + 1) // 2, Ta)):] = 0.0
+        au = [au.to(dev).to(dtype)]
+    return Batch(query.to(dev), his.to(dev), fts.to(dev).to(dtype), cap.to(dev), trg.to(dev), trg_y.to(dev), audio_fts=au)

@@ -284,7 +284,7 @@ def xent_smooth_losses(logits: Tensor, target: Tensor, denom, smoothing: float, 
 
 def switch_logits_ok(w: Tensor, bias: Optional[Tensor], parts) -> bool:
     d = parts[0].shape[-1]
-    return (POINTER_ATTN and w.is_cuda and w.dtype in (torch.bfloat16, torch.float32) and 1 <= len(parts) <= 4 and w.shape[0] <= 4
+    return (POINTER_ATTN and w.is_cuda and w.dtype in (torch.bfloat16, torch.float32) and 1 <= len(parts) <= 5 and w.shape[0] <= 4
             and w.shape[1] == len(parts) * d and d % 8 == 0 and w.stride(1) == 1 and w.stride(0) % 8 == 0 and w.data_ptr() % 16 == 0
             and all(p.dtype == w.dtype and p.shape[-1] == d and p.numel() == parts[0].numel() for p in parts) and (bias is None or bias.dtype == w.dtype))
 

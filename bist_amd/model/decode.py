@@ -251,7 +251,8 @@ def _graph_step_incr(model, bn, fn, new_tokens, pos, slot0, mask_np, train_args,
     return out if shared is not None else out.cpu().numpy()
 
 
-_TURN_FIELDS = ("query", "his", "cap", "fts", "query_mask", "query_mask2", "his_mask", "cap_mask", "temporal_mask")
+_TURN_FIELDS = ("query", "his", "cap", "fts", "query_mask", "query_mask2", "his_mask", "cap_mask", "temporal_mask", "audio_fts", "audio_mask")
+AUDIO_BUCKET = 32      # the audio length of a turn's static buffers: the next multiple of this many rows (zero rows, masked by construction)
 
 
 _BUCKETED_FIELDS = {"query": "pad", "his": "pad", "cap": "pad", "query_mask": 0, "query_mask2": 0, "his_mask": 0, "cap_mask": 0}
@@ -261,6 +262,10 @@ def _staged_shape(f, v, bucket):
     """Shape of field f in the static buffers of a turn's graphs: the token tensors and their masks reach up to the next multiple of the
     length bucket (see BUCKET: padded positions carry the pad id and a False mask, so nothing reads them; dataset.py:66-67, 92 build the masks from the pad id)."""
     shp = tuple(v.shape)
+    if bucket and f == "audio_fts":           # [B, Ta, Da]: zero rows appended (a zero row sums to zero: dataset.py:87 masks it)
+        return (shp[0], -(-shp[1] // AUDIO_BUCKET) * AUDIO_BUCKET, shp[2])
+    if bucket and f == "audio_mask":          # [B, 1, Ta]
+        return shp[:-1] + (-(-shp[-1] // AUDIO_BUCKET) * AUDIO_BUCKET,)
     if f not in _BUCKETED_FIELDS or not bucket:
         return shp
     L = shp[-1]
@@ -299,7 +304,10 @@ def _graph_first_step(model, batch, start_symbol, train_args, host=True, pad_sym
             v = getattr(batch, f, None)
             if v is not None:
                 pad = _BUCKETED_FIELDS.get(f, 0)
-                jobs.append((v if v.is_contiguous() else v.contiguous(), getattr(sb, f), pad_symbol if pad == "pad" else pad))
+                v, dst = v if v.is_contiguous() else v.contiguous(), getattr(sb, f)
+                if f == "audio_fts":          # rows appended per clip: each clip is one row of Ta * Da elements with a zero tail
+                    v, dst = v.view(v.shape[0], -1), dst.view(dst.shape[0], -1)
+                jobs.append((v, dst, pad_symbol if pad == "pad" else pad))
         ops.stage_inputs(jobs)
     # A geometry seen before: stage and launch first, check the graphs against the parameters' values while the device runs (the walk
     # over ~900 parameters costs 0.2 ms of host time with the device idle otherwise).  Stale graphs -- the parameters were written

@@ -25,6 +25,11 @@ def ag_fuse_one() -> bool:
 
 FUSE_ON_DEC = os.environ.get("BIST_FUSE_ON_DEC", "1") != "0"      # training: the modality fusion on the decoder layers' stream (0: on the main stream)
 CAP_OWN_CHAIN = os.environ.get("BIST_CAP_CHAIN", "1") != "0"      # tuning aid: 0 = the caption layers of a training step on the decoder layers' stream
+# training: where the audio layer of a block runs.  "cap": behind the block's caption layer on its chain; "main": on the main chain, behind the
+# visual layer; "auto" (default): "cap" where the caption layers have a chain of their own (the fourth chain of the split executor), "main"
+# on three streams -- there the caption / decoder stream is the longest per block (decoder layer + caption layer) and the main chain has the
+# slack
+AUDIO_CHAIN = os.environ.get("BIST_AUDIO_CHAIN", "auto")
 FAN_JOIN = os.environ.get("BIST_FAN_JOIN", "1") != "0"      # 0 = the gradient sums of the multi-stream fans rely on the engine's ordering alone
 
 
@@ -68,6 +73,8 @@ class MultimodalDecoderLayer12(nn.Module):
                     tx = _cross_attention(s[cnt], a[cnt], x, ft["temporal_ft"], b.query_mask); cnt += 1
                     sx = _cross_attention(s[cnt], a[cnt], x, ft["spatial_ft"], b.query_mask); cnt += 1
                     x = Fn.add(tx, sx)
+            if getattr(args, "nb_aenc_blocks", 0) > 0:                                                   # :55-57
+                x = _cross_attention(s[cnt], a[cnt], x, ft["audio_ft"], b.query_mask); cnt += 1
         return _feed_forward(s[cnt], self.ff, x)                                                         # :58
 
 
@@ -86,8 +93,6 @@ class MultimodalDecoder8(nn.Module):
         self.N, self.v_N, self.c_N, self.a_N = N, venc_N, cenc_N, aenc_N
         self.norm = LayerNorm(layer.size)
         self.args = args
-        if aenc_N > 0:
-            raise NotImplementedError("audio reasoning is outside the hot path (SURVEY.md 8a)")
         if self.v_N > 0:
             if args.enc_st_combine != "none":
                 raise NotImplementedError("enc_st_combine=%s is outside the hot path: multi-layer models only run "
@@ -98,8 +103,14 @@ class MultimodalDecoder8(nn.Module):
         if self.c_N > 0:
             self.c_layers = clones(c_layer, self.c_N)
             self.cap_out_norm = LayerNorm(c_layer.size)
+        if self.a_N > 0:                                                                       # decoder.py:87-89
+            self.a_layers = clones(a_layer, self.a_N)
+            self.a_out_norm = LayerNorm(a_layer.size)
         if self.v_N > 0 and args.enc_vc_combine == "dyn":
-            factor = 1 + (args.include_caption != "none") + bool(args.t2s) + bool(args.s2t)    # decoder.py:95-103
+            if self.a_N > 0 and not (args.t2s and args.s2t):
+                raise NotImplementedError("audio with one visual direction under enc_vc_combine='dyn': the reference indexes a score "
+                                          "column that does not exist (decoder.py:160-167)")
+            factor = 1 + (args.include_caption != "none") + bool(args.t2s) + bool(args.s2t) + (self.a_N > 0)    # decoder.py:95-103
             self.vc_combine_W = nn.Linear(v_layer.size * factor, factor - 1)
 
     def _fuse(self, ft: Dict[str, Tensor]) -> None:
@@ -121,6 +132,8 @@ class MultimodalDecoder8(nn.Module):
             parts.append(Fn.fan_take(ft, "spatial_ft"))
         if args.s2t:
             parts.append(Fn.fan_take(ft, "temporal_ft"))
+        if self.a_N > 0:                                   # (both directions: __init__ refuses the other cases)
+            parts.append(Fn.fan_take(ft, "audio_ft"))                                         # decoder.py:153-154, 174-175
         W, bias = self.vc_combine_W.weight, self.vc_combine_W.bias
         d = parts[0].shape[-1]
         if W.shape[1] != d * len(parts):
@@ -128,8 +141,9 @@ class MultimodalDecoder8(nn.Module):
         if (torch.is_grad_enabled() and self.c_N > 0 and args.t2s and args.s2t and parts[0].is_cuda
                 and all(p.is_contiguous() for p in parts)):
             # training: the fusion logits and the weighted sum as ONE autograd node -- every modality tensor has one consumer here instead of
-            # two (autograd.FuseDynFn); parts = [query, cap, spatial, temporal], score column j -> temporal, spatial, cap (decoder.py:156-159)
-            ft["encoded_ft"] = Fn.fuse_dyn(W, bias, parts, (3, 2, 1))
+            # two (autograd.FuseDynFn); parts = [query, cap, spatial, temporal (, audio)], score column j -> temporal, spatial, cap (, audio)
+            # (decoder.py:156-159, 166-167): with audio five parts and four logits, still ONE node and one logits launch
+            ft["encoded_ft"] = Fn.fuse_dyn(W, bias, parts, (3, 2, 1, 4) if self.a_N > 0 else (3, 2, 1))
             return
         if torch.is_grad_enabled() and ag_fuse_one() and Fn.switch_logits_ok(W, bias, parts):
             # training without the one-node form (a direction or the caption stack switched off): the same one-launch logits as autograd.FuseDynFn
@@ -139,9 +153,10 @@ class MultimodalDecoder8(nn.Module):
             for j, p in enumerate(parts):                  # concat order: query, cap, spatial, temporal
                 score = Fn.linear(p, Fn.column_block(W, j, d), bias if j == 0 else None, out=score, accumulate=j > 0)
         # score column -> modality (decoder.py:156-165): 0 temporal, 1 spatial, 2 cap (both directions);
-        # one direction: 0 that direction, 1 cap.  Without a caption layer: 0 temporal, 1 spatial.
+        # one direction: 0 that direction, 1 cap.  Without a caption layer: 0 temporal, 1 spatial.  Audio takes the column after
+        # these: 3 with a caption stack, 2 without (decoder.py:166-167, 180-181).
         if args.t2s and args.s2t:
-            xs = [ft["temporal_ft"], ft["spatial_ft"]] + ([ft["cap_ft"]] if self.c_N > 0 else [])
+            xs = [ft["temporal_ft"], ft["spatial_ft"]] + ([ft["cap_ft"]] if self.c_N > 0 else []) + ([ft["audio_ft"]] if self.a_N > 0 else [])
         elif args.s2t:
             xs = [ft["temporal_ft"], ft["cap_ft"]]
         else:
@@ -370,7 +385,7 @@ class MultimodalDecoder8(nn.Module):
         return out.view(n, Lt, d)
 
     # Keys the reasoning layers write per decoder layer (decoder.py:126-181); everything else in ``ft`` is static.
-    _REASONING_KEYS = ("temporal_ft", "spatial_ft", "cap_ft", "encoded_ft")
+    _REASONING_KEYS = ("temporal_ft", "spatial_ft", "cap_ft", "audio_ft", "encoded_ft")
     REASONING_CACHE = True      # inference only; set False to recompute the reasoning on every decode() like the reference
 
     def forward(self, b, ft: Dict[str, Tensor], x: Tensor) -> Dict[str, Tensor]:
@@ -396,11 +411,23 @@ class MultimodalDecoder8(nn.Module):
             # accumulation is a pairwise elementwise launch per extra reader): the query feeds the three reasoning chains, every layer's
             # fusion logits and decoder layer, and two readers per pointer attention; the caption every caption layer and its pointer
             L_ = len(self.layers)
-            Fn.fan_set(ft, "encoded_query", 3 + 2 * L_ + 2, join=FAN_JOIN)
+            Fn.fan_set(ft, "encoded_query", 3 + 2 * L_ + 2 + (self.a_N > 0), join=FAN_JOIN)
             Fn.fan_set(ft, "encoded_his", L_ + 2, join=FAN_JOIN)
             Fn.fan_set(ft, "encoded_cap", L_ + 2, join=FAN_JOIN)
+            if self.a_N > 0:
+                Fn.fan_set(ft, "encoded_audio", L_, join=FAN_JOIN)      # one reader per audio layer
         q = ft["encoded_query"]
-        in_ft = {"t2s": Fn.fan_take(ft, "encoded_query"), "s2t": Fn.fan_take(ft, "encoded_query"), "audio": q, "cap": Fn.fan_take(ft, "encoded_query")}
+        in_ft = {"t2s": Fn.fan_take(ft, "encoded_query"), "s2t": Fn.fan_take(ft, "encoded_query"),
+                 "audio": Fn.fan_take(ft, "encoded_query") if self.a_N > 0 else q, "cap": Fn.fan_take(ft, "encoded_query")}
+
+        def audio_layer(l, in_ft):
+            """Audio reasoning layer l and its output norm (decoder.py:133-135), on the stream it is called on."""
+            in_ft["audio"] = STM.through(in_ft["audio"], "audio in", True)
+            in_ft = self.a_layers[l](in_ft, ft, b)
+            in_ft["audio"] = STM.through(in_ft["audio"], "audio out", True)
+            n_ = self.a_out_norm
+            ft["audio_ft"], in_ft["audio"] = Fn.layernorm_res(in_ft["audio"], n_.a_2, n_.b_2, n_.eps)
+            return in_ft
         fused_train = False
         if self.v_N > 0 and "spatiotemporal_ft" in ft:
             # training: the video tensor feeds 4 products per reasoning layer (2 score products, 2 value projections); their [B*T*S, d] gradients are summed in one pass
@@ -479,6 +506,11 @@ class MultimodalDecoder8(nn.Module):
                     in_ft = self.c_layers[l](in_ft, ft, b)
                     in_ft["cap"] = STM.through(in_ft["cap"], "cap out", True)
                     ft["cap_ft"], in_ft["cap"] = Fn.layernorm_res(in_ft["cap"], self.cap_out_norm.a_2, self.cap_out_norm.b_2, self.cap_out_norm.eps)                           # decoder.py:132
+                    audio_main = self.a_N > 0 and torch.is_grad_enabled() and (AUDIO_CHAIN == "main" or (AUDIO_CHAIN == "auto" and cside is side))
+                    if self.a_N > 0 and not audio_main:
+                        # the audio layer rides the caption layers' chain, behind this block's caption layer: like it, it reads the encoded
+                        # query side only, and with a chain of their own the two have the slack (the main chain carries the visual layer)
+                        in_ft = audio_layer(l, in_ft)
             if self.v_N > 0:
                 if torch.is_grad_enabled():
                     ft["_bist_out_norms"] = (self.spatial_out_norm, self.temporal_out_norm)
@@ -498,18 +530,22 @@ class MultimodalDecoder8(nn.Module):
                         # next layer on a side stream, and the chain would put two cross-stream hops per layer on that direction's backward
                         n_ = self.spatial_out_norm
                         ft["spatial_ft"], in_ft["t2s"] = Fn.layernorm_res(in_ft["t2s"], n_.a_2, n_.b_2, n_.eps)      # :129
+            if fork_cap and audio_main:
+                in_ft = audio_layer(l, in_ft)     # three streams: on the main chain, under the caption / decoder stream's longer block
             if fork_cap:
                 main.wait_stream(cside)
             elif self.c_N > 0:
                 in_ft = self.c_layers[l](in_ft, ft, b)
                 ft["cap_ft"], in_ft["cap"] = Fn.layernorm_res(in_ft["cap"], self.cap_out_norm.a_2, self.cap_out_norm.b_2, self.cap_out_norm.eps)                               # :132
+            if self.a_N > 0 and not fork_cap:
+                in_ft = audio_layer(l, in_ft)                                                                                                                                      # :133-135
             if torch.is_grad_enabled() and conc_keep:
                 # every tensor handed from one stream's chain to another's at this layer boundary (see Fn._keep_taken)
-                for t_ in (*[v for v in in_ft.values() if torch.is_tensor(v)], ft.get("cap_ft"), ft.get("spatial_ft"), ft.get("temporal_ft")):
+                for t_ in (*[v for v in in_ft.values() if torch.is_tensor(v)], ft.get("cap_ft"), ft.get("spatial_ft"), ft.get("temporal_ft"), ft.get("audio_ft")):
                     Fn._keep_taken(t_)
             if torch.is_grad_enabled() and l + 1 == len(self.layers) and getattr(self.args, "auto_encoder", 0):
                 # the last layer's outputs also feed the auto-encoder heads (optimize.py:66-82): an alias per consumer, one-pass gradient sum
-                for k_ in ("cap_ft", "spatial_ft", "temporal_ft"):
+                for k_ in ("cap_ft", "spatial_ft", "temporal_ft", "audio_ft"):
                     Fn.fan_set(ft, k_, 2)
             STM.lmark("main joined")
             # Training with the decoder layer pipelined onto the caption / decoder stream: the fusion of the modalities (decoder.py:140-165) goes

@@ -63,15 +63,18 @@ class VidEncoder8(nn.Module):
     def __init__(self, W, a_W, vid_position, v_N, a_N, size, args):
         super().__init__()
         self.v_N, self.a_N, self.args = v_N, a_N, args
-        if a_N > 0:
-            raise NotImplementedError("audio features are outside the hot path (SURVEY.md 8a; the reference's audio "
-                                      "branch reads the undefined args.noW_venc, encoder.py:84)")
+        if vid_position is not None:
+            raise NotImplementedError("vid_position is always None in the reference (mtn.py:106)")
+        if v_N > 0 or a_N > 0:
+            self.vid_position = vid_position
         if v_N > 0:
             self.W = W
-            self.vid_position = vid_position
             self.in_norm = LayerNorm(size)
-            if vid_position is not None:
-                raise NotImplementedError("vid_position is always None in the reference (mtn.py:106)")
+        if a_N > 0:                                     # encoder.py:67-70
+            if a_W is None:
+                raise ValueError("nb_aenc_blocks > 0 needs the audio feature width: ft_sizes=[C, Da] (mtn.py:113)")
+            self.a_W = a_W
+            self.a_in_norm = LayerNorm(size)
 
     def forward(self, b, ft: Dict[str, Tensor]) -> Dict[str, Tensor]:
         if self.v_N > 0:
@@ -96,6 +99,25 @@ class VidEncoder8(nn.Module):
             else:
                 act = Fn.linear(fts.reshape(B * T * S, C), self.W.weight, self.W.bias, act=Fn.ACT_RELU)
                 ft["spatiotemporal_ft"] = self.in_norm(act).view(B, T, S, -1)
+        if self.a_N > 0:
+            # ft['encoded_audio'] = a_in_norm(ReLU(a_W audio_fts))   (encoder.py:83-91; the reference reads args.noW_venc, which no
+            # config defines: absent counts as false)
+            au = b.audio_fts
+            if au is None:
+                raise ValueError("this model has audio reasoning layers: the batch needs audio_fts [B, Ta, Da]")
+            n = self.a_in_norm
+            if au.dtype != n.a_2.dtype:
+                au = Fn.cast(au, n.a_2.dtype)
+            B, Ta, Da = au.shape
+            if getattr(self.args, "noW_venc", False):
+                ft["encoded_audio"] = n(au)              # features of the model width, used as they are (encoder.py:84-85)
+            elif not torch.is_grad_enabled() and au.is_cuda:
+                # inference: one launch through the product's LayerNorm epilogue where it covers the shape, as the video stage above
+                y = ops.linear(au.reshape(B * Ta, Da), self.a_W.weight, self.a_W.bias, act=Fn.ACT_RELU, ln_out=(n.a_2, n.b_2, n.eps))
+                ft["encoded_audio"] = y.view(B, Ta, -1)
+            else:
+                act = Fn.linear(au.reshape(B * Ta, Da), self.a_W.weight, self.a_W.bias, act=Fn.ACT_RELU)
+                ft["encoded_audio"] = n(act).view(B, Ta, -1)
         return ft
 
 
@@ -516,8 +538,7 @@ class CapEncoderLayer(nn.Module):
 
 
 class AudioEncoderLayer(nn.Module):
-    """Parameter container only (the reference builds one even with nb_aenc_blocks == 0, mtn.py:131);
-    its forward is outside the hot path."""
+    """Self-attention, attention to the encoded audio, FFN (reference: encoder.py:220-235): CapEncoderLayer on the audio memory."""
 
     def __init__(self, size, attn, nb_attn, ff, dropout):
         super().__init__()
@@ -527,4 +548,7 @@ class AudioEncoderLayer(nn.Module):
         self.sublayer = clones(SublayerConnection(size, dropout), nb_attn + 1)
 
     def forward(self, in_ft, ft, b):
-        raise NotImplementedError("audio reasoning is outside the hot path (SURVEY.md 8a)")
+        a = _self_attention(self.sublayer[0], self.attn[0], in_ft["audio"], b.query_mask)
+        a = _cross_attention(self.sublayer[1], self.attn[1], a, Fn.fan_take(ft, "encoded_audio"), b.audio_mask)
+        in_ft["audio"] = _feed_forward(self.sublayer[2], self.ff, a)
+        return in_ft

@@ -54,6 +54,8 @@ class SimpleLossCompute:
         if a.auto_encoder:
             if a.nb_cenc_blocks > 0:
                 keys.append(("cap_ae", "cap_ft"))
+            if getattr(a, "nb_aenc_blocks", 0) > 0:                                                      # optimize.py:61-65
+                keys.append(("audio_ae", "audio_ft"))
             if a.nb_venc_blocks > 0 and a.enc_st_combine == "none":
                 if a.s2t:
                     keys.append(("temporal_ae", "temporal_ft"))

@@ -677,6 +677,32 @@ def stage_train_batch(src, dst, pad: int) -> None:
     check(lib.bist_stage_train_batch(C.byref(d), _stream()), "bist_stage_train_batch")
 
 
+def stage_audio(src: Tensor, dst: Tensor, mask: Tensor) -> None:
+    """bist_stage_audio: audio features `src` [B, Ta, Da] (f32 / bf16) into the preallocated class buffer `dst` [B, PTa >= Ta, Da]
+    (compute dtype; tail rows zero) and `mask` bool [B, 1, PTa] by the reference's sum rule over the source values (dataset.py:83-87).
+    One launch on the current stream; capturable."""
+    _dev(src, dst, mask)
+    if (src.dim() != 3 or dst.dim() != 3 or not src.is_contiguous() or not dst.is_contiguous() or src.shape[0] != dst.shape[0]
+            or src.shape[2] != dst.shape[2] or dst.shape[1] < src.shape[1] or src.numel() == 0):
+        raise ValueError("bist_amd.stage_audio: features [B, Ta, Da] into a contiguous [B, PTa >= Ta, Da]")
+    B, Ta, Da = src.shape
+    PTa = dst.shape[1]
+    if mask.dtype != torch.bool or not mask.is_contiguous() or tuple(mask.shape) != (B, 1, PTa):
+        raise ValueError(f"bist_amd.stage_audio: audio_mask must be a contiguous bool tensor of shape {(B, 1, PTa)}, got {tuple(mask.shape)} {mask.dtype}")
+    check(lib.bist_stage_audio(src.data_ptr(), dst.data_ptr(), mask.data_ptr(), B, Ta, PTa, Da, dtype_code(src.dtype), dtype_code(dst.dtype),
+                               _stream()), "bist_stage_audio")
+
+
+def audio_mask(audio_fts: Tensor) -> Tensor:
+    """(audio_fts.sum(-1) != 0).unsqueeze(-2) of data/dataset.py:83-87 on the device: bist_temporal_mask with row_elems = Da."""
+    _dev(audio_fts)
+    B, Ta, Da = audio_fts.shape
+    f = audio_fts.contiguous()
+    m = torch.empty((B, 1, Ta), device=f.device, dtype=torch.uint8)
+    check(lib.bist_temporal_mask(f.data_ptr(), m.data_ptr(), B * Ta, Da, dtype_code(f.dtype), _stream()), "bist_temporal_mask")
+    return m.view(torch.bool)
+
+
 def eval_accumulate(terms: Sequence[Tensor], term_counts: Sequence[Tensor], counts: Sequence[Tensor], totals: Tensor,
                     count_totals: Tensor) -> None:
     """bist_eval_accumulate: totals[k] += terms[k] * term_counts[k] (f32 scalars times int64 scalars, summed in double),

@@ -237,14 +237,14 @@ class Trainer:
         place(lut)                                        # ... and the shared embedding matrix
         n_prefix_params = len(order)
         # The matrices behind the prefix, grouped into PIECES in the order the forward pass first reads them: piece 0 = everything
-        # outside the layer stacks (input projection, text encoders, generator), piece 1 + l = reasoning / caption / decoder layer l.
+        # outside the layer stacks (input projections, text encoders, generator), piece 1 + l = reasoning / caption / audio / decoder layer l.
         # Within a piece the packed attention weights come first.  (The deferred optimiser updates piece by piece.)
         names = {}
         for nme, p in model.named_parameters():
             names.setdefault(id(p), nme)
 
         def piece_of(p) -> int:
-            mt = re.match(r"mutlimodal_decoder\.(?:v_layers|c_layers|layers)\.(\d+)\.", names.get(id(p), ""))
+            mt = re.match(r"mutlimodal_decoder\.(?:v_layers|c_layers|a_layers|layers)\.(\d+)\.", names.get(id(p), ""))
             return 1 + int(mt.group(1)) if mt else 0
         units = []                                        # (piece, kind, sequence, [parameters placed back to back])
         for i, m in enumerate(attns):
@@ -746,7 +746,7 @@ class Trainer:
 
     # ---- hipGraph path: forward + backward + gradient fold captured once per batch geometry ----------------
     _BATCH_FIELDS = ("query", "his", "cap", "trg", "trg_y", "fts", "query_mask", "query_mask2", "his_mask", "cap_mask", "temporal_mask",
-                     "trg_mask", "trg_mean_mask", "ntokens", "qntokens")
+                     "trg_mask", "trg_mean_mask", "ntokens", "qntokens", "audio_fts", "audio_mask")
 
     def _shape_key(self, batch):
         return tuple((f, tuple(getattr(batch, f).shape), getattr(batch, f).dtype) for f in self._BATCH_FIELDS
@@ -857,6 +857,10 @@ class Trainer:
         own.trg_mean_mask = mask(B, Pt) if batch.trg_y is not None else None
         own.ntokens = torch.zeros((), dtype=torch.int64, device=dev) if batch.ntokens is not None else None
         own.qntokens = torch.zeros((), dtype=torch.int64, device=dev)
+        if getattr(batch, "audio_fts", None) is not None:
+            PTa = shp["audio"]
+            own.audio_fts = torch.empty((B, PTa, batch.audio_fts.shape[2]), dtype=self.compute_dtype, device=dev)
+            own.audio_mask = mask(B, 1, PTa)
         return own
 
     def _stage(self, batch, static) -> None:
@@ -871,6 +875,9 @@ class Trainer:
                 if t is not None:
                     setattr(src, f, t.contiguous())
         ops.stage_train_batch(src, static, self._pad)
+        au = getattr(batch, "audio_fts", None)
+        if au is not None:                                         # the audio rows, their zero tail and audio_mask: one more launch
+            ops.stage_audio(au if au.is_contiguous() else au.contiguous(), static.audio_fts, static.audio_mask)
 
     def _capture_class(self, batch, key) -> "_GraphEntry":
         while len(self._entries) >= self.max_graphs:
@@ -920,6 +927,8 @@ class Trainer:
         if a.auto_encoder:
             if a.nb_cenc_blocks > 0:
                 names.append("cap_ae")
+            if getattr(a, "nb_aenc_blocks", 0) > 0:
+                names.append("audio_ae")
             if a.nb_venc_blocks > 0 and a.enc_st_combine == "none":
                 names += (["temporal_ae"] if a.s2t else []) + (["spatial_ae"] if a.t2s else [])
         return names
@@ -1032,7 +1041,7 @@ class Trainer:
 
     def evaluate(self, batches) -> Dict[str, float]:
         """The reference's validation pass (train.py:21-52 with eval=True) over an iterable of device batches or a DeviceFeeder: the
-        per-token averages ``out``, ``temporal_ae``, ``spatial_ae`` (and ``cap_ae`` where that head exists) -- sums of un-normalised
+        per-token averages ``out``, ``temporal_ae``, ``spatial_ae`` (and ``cap_ae`` / ``audio_ae`` where those heads exist) -- sums of un-normalised
         terms over summed token counts, as run_epoch returns them -- plus ``tokens``, ``qtokens`` and ``batches``.  The sums are kept on
         the device by every step's tail launch and read once, here.  Several ranks: each evaluates its own shard, the totals are
         summed with one all-reduce, and every rank returns the same token-weighted global averages.  A model without the temporal or
@@ -1053,8 +1062,9 @@ class Trainer:
             raise ValueError("bist_amd.Trainer.evaluate: no tokens to average over (an empty validation set?)")
         out = {"out": tot["out"] / tokens, "temporal_ae": tot.get("temporal_ae", 0.0) / qtokens,
                "spatial_ae": tot.get("spatial_ae", 0.0) / qtokens}
-        if "cap_ae" in tot:
-            out["cap_ae"] = tot["cap_ae"] / qtokens
+        for k in ("cap_ae", "audio_ae"):
+            if k in tot:
+                out[k] = tot[k] / qtokens
         out.update(tokens=tokens, qtokens=qtokens, batches=nb)
         return out
 

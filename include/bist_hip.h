@@ -598,10 +598,12 @@ int bist_xent_smooth_bwd(const float* logits, const float* lse, const int64_t* t
                          int32_t pad, void* stream);
 int bist_sum_div_groups(const float* x, int64_t M, int32_t G, const int64_t* denom, float* out, int32_t out_stride, void* stream);
 int bist_stack_rows(const void* const* srcs, int32_t n, void* out, int64_t bytes_each, void* stream);
-/* A small linear layer over the CONCATENATION of n_parts <= 4 tensors [rows][d] without the concatenation: part j multiplies column block
+/* A small linear layer over the CONCATENATION of n_parts <= 5 tensors [rows][d] without the concatenation: part j multiplies column block
  * j of W [ns <= 4][ldw >= n_parts d]; out [rows][ns] = sum_j part_j . W_j^T + bias, f32 or (out_dtype) the operand dtype.  The switch logits
  * of (Multi)PointerGenerator (model/generator.py:69-71, 119-121: pointer_gen_W(torch.cat(parts, -1))) and the fusion logits of
- * MultimodalDecoder8 (model/decoder.py:142-159: vc_combine_W(torch.cat(...))).
+ * MultimodalDecoder8 (model/decoder.py:142-159: vc_combine_W(torch.cat(...)); with the audio stack five parts -- query, cap, spatial,
+ * temporal, audio, decoder.py:148-154 -- and four logits).  Calls with <= 4 parts compute what they computed under the earlier limit
+ * of four, bit for bit: the per-row order over parts and columns and the weight-gradient grid (n_parts x column chunks) are unchanged.
  * Backward: dsw [rows][ns] f32 or (dsw_dtype) the operand dtype; dparts[j] = dsw . W_j (+ residuals[j]: an addend of that part's gradient
  * from elsewhere, e.g. the fusion's weighted sum) written (entries / the arrays may be NULL), dW [ns][lddw] and db [ns] written or
  * accumulated (dW NULL = not wanted; db only together with dW).  parts / dparts / residuals are HOST arrays of n_parts pointers.        */
@@ -784,6 +786,16 @@ typedef struct BistTrainStage {
   int32_t B; int32_t T; int32_t PT; int32_t fts_dtype; int32_t out_dtype; int32_t reserved_;
 } BistTrainStage;
 int bist_stage_train_batch(const BistTrainStage* desc, void* stream);
+
+/* Audio features of EXACT length staged into the CLASS-shaped audio buffer of a captured step as ONE launch (csrc/stage_audio.hip;
+ * the reference pads audio to the batch's longest clip and derives audio_mask = (audio_fts.sum(-1) != 0).unsqueeze(-2),
+ * data/dataset.py:60, 83-87): src [B, Ta, Da] (src_dtype f32 / bf16, contiguous) -> dst [B, PTa >= Ta, Da] in out_dtype with the
+ * rounding of bist_cast, zero rows appended from Ta to PTa; mask [B, PTa] bool bytes from the SOURCE values, bit-identical to
+ * bist_temporal_mask(row_elems = Da) over the zero-padded source (the same per-row summation order, so a row whose entries cancel is
+ * masked exactly where Batch masks it).  16-byte vectors when Da is a multiple of both dtypes' vector widths and both bases are
+ * 16-byte aligned, single elements otherwise; any Da >= 1.  No allocation, no host synchronisation: capturable.                    */
+int bist_stage_audio(const void* src, void* dst, uint8_t* mask, int32_t B, int32_t Ta, int32_t PTa, int32_t Da, int32_t src_dtype,
+                     int32_t out_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The running totals of a validation pass (train.py:32-37 with eval=True: total_loss += loss, total_tokens += batch.ntokens, ...;
