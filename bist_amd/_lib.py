@@ -14,7 +14,7 @@ GRAD_SUMSQ_MAX_SLOTS = 4096      # BIST_GRAD_SUMSQ_MAX_SLOTS (include/bist_hip.h
 STATE_MAX_SLOTS = 4096           # BIST_STATE_MAX_SLOTS (include/bist_hip.h)
 ACT_NONE, ACT_RELU, ACT_GATE = 0, 1, 2
 # kernel families of bist_launch_count (include/bist_hip.h: BIST_K_*)
-K_ST1_MFMA_FWD, K_ST1_MFMA_BWD, K_ST1_VALU, K_ST2_MFMA_FWD, K_ST2_MFMA_BWD, K_ST2_VALU, K_MHA_FWD, K_MHA_BWD_MFMA, K_MHA_BWD_VALU, K_ST1_FUSED, K_DECSTACK, K_ST1_FUSED_TRAIN, K_ST1_PBWD, K_MHA_FWD_DK64 = range(14)
+K_ST1_MFMA_FWD, K_ST1_MFMA_BWD, K_ST1_VALU, K_ST2_MFMA_FWD, K_ST2_MFMA_BWD, K_ST2_VALU, K_MHA_FWD, K_MHA_BWD_MFMA, K_MHA_BWD_VALU, K_ST1_FUSED, K_DECSTACK, K_ST1_FUSED_TRAIN, K_ST1_PBWD, K_MHA_FWD_DK64, K_GEMM_KSEG, K_ADD_N = range(16)
 
 
 class BistGemm(C.Structure):
@@ -36,6 +36,24 @@ class BistGemm(C.Structure):
         ("ln_mode", C.c_int32),
         ("bias_bs1", C.c_int64),
     ]
+
+
+GEMM_KSEG_MAX = 24               # BIST_GEMM_KSEG_MAX (include/bist_hip.h)
+
+
+class BistGemmSeg(C.Structure):
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p),
+                ("a_rs", C.c_int64), ("a_ks", C.c_int64), ("a_bs1", C.c_int64), ("a_bs2", C.c_int64),
+                ("b_rs", C.c_int64), ("b_ks", C.c_int64), ("b_bs1", C.c_int64), ("b_bs2", C.c_int64),
+                ("K", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BistGemmKSeg(C.Structure):
+    _fields_ = [("C", C.c_void_p), ("residual", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32),
+                ("ldc", C.c_int64), ("ldr", C.c_int64), ("batch1", C.c_int32), ("batch2", C.c_int32),
+                ("c_bs1", C.c_int64), ("c_bs2", C.c_int64), ("r_bs1", C.c_int64), ("r_bs2", C.c_int64),
+                ("alpha", C.c_float), ("in_dtype", C.c_int32), ("out_dtype", C.c_int32), ("nseg", C.c_int32),
+                ("seg", BistGemmSeg * GEMM_KSEG_MAX)]
 
 
 class BistDrop(C.Structure):
@@ -113,6 +131,8 @@ SIGNATURES = {
     "bist_gemm_pair": (C.c_int, [C.POINTER(BistGemm), C.POINTER(BistGemm), _P]),
     "bist_gemm_is_fast": (C.c_int, [C.POINTER(BistGemm)]),
     "bist_gemm_ln_ok": (C.c_int, [C.POINTER(BistGemm)]),
+    "bist_gemm_kseg_ok": (C.c_int, [C.POINTER(BistGemmKSeg)]),
+    "bist_gemm_kseg": (C.c_int, [C.POINTER(BistGemmKSeg), _P]),
     "bist_layernorm_fwd": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _I64, _F, _I32, _P]),
     "bist_layernorm_fwd_multi": (C.c_int, [C.POINTER(BistLnSet), _I32, _I64, _I32, _I64, _I64, _F, _I32, _P]),
     "bist_layernorm_bwd_multi": (C.c_int, [C.POINTER(BistLnBwdSet), _I32, _I64, _I32, _I64, _I64, _I64, _F, _I64, C.POINTER(BistDrop), _I32, _P]),

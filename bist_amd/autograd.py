@@ -96,6 +96,67 @@ class _Leaf:
         return False
 
 
+# ----------------------------------------------------------------------------------------------
+# the video tensor's gradient as K-segmented products (FanOutFn's sink)
+# ----------------------------------------------------------------------------------------------
+VIDEO_GRAD_SEG_DEFAULT = "1"
+
+
+def _seg_on() -> bool:
+    """BIST_VIDEO_GRAD_SEG (0 = every term a product of its own, summed by bist_add_n), read per backward node so that one process can
+    run both forms."""
+    return os.environ.get("BIST_VIDEO_GRAD_SEG", VIDEO_GRAD_SEG_DEFAULT) != "0"
+
+
+class _Sink(list):
+    """Pending segments of ONE FanOutFn instance: a producer whose input alias carries the sink (attribute ``_bist_sink``, set by
+    functional.Fan) appends the operands of its term instead of launching the product, and FanOutFn.backward forms all terms in one
+    bist_gemm_kseg launch per operand layout.  Entries: (kind, segment of ops.kseg, alpha, event, operands kept alive)."""
+    __slots__ = ()
+
+
+def _seg_placeholder(shape, like: Tensor, sink: "_Sink") -> Tensor:
+    """What a producer returns in place of the gradient it left in the sink: a zero-stride tensor of the gradient's shape that is never
+    read, marked with the sink it belongs to (travels as ``_bist_dz`` / ``_bist_ready`` do: on this very tensor object)."""
+    ph = torch.empty((1,), device=like.device, dtype=like.dtype).expand(tuple(shape))
+    ph._bist_seg = sink
+    return ph
+
+
+def _seg_push(sink: "_Sink", kind: str, seg, alpha: float, keep) -> None:
+    ev = torch.cuda.Event()
+    ev.record()                       # the operands are final at this point of the producer's stream; FanOutFn waits for it
+    sink.append((kind, seg, float(alpha), ev, keep))
+
+
+def _score_seg(dsc: Tensor, q3: Tensor, B: int, R: int, TS: int):
+    return ops.kseg(dsc, q3, R, a_rs=1, a_ks=TS, a_bs=(R * TS, 0), b_rs=1, b_ks=q3.stride(1), b_bs=(q3.stride(0), 0))
+
+
+def _weight_now(w: Tensor) -> Tensor:
+    """The weight a value term reads: itself, or -- when the trainer updates parameters inside the backward pass (ops.SEG_SNAPSHOT_W) -- a
+    copy taken now, on the producer's stream, where the product of its own would have read it (the same bits either way)."""
+    if not ops.SEG_SNAPSHOT_W:
+        return w
+    src = w.detach() if w.is_contiguous() else w.detach().contiguous()
+    return ops.copy_into(torch.empty_like(src), src)
+
+
+def _value_seg(dz: Tensor, w: Tensor, TS: int):
+    N = w.shape[0]
+    return ops.kseg(dz, w, N, a_rs=N, a_ks=1, a_bs=(TS * N, 0), b_rs=1, b_ks=w.stride(0), b_bs=(0, 0))
+
+
+def _seg_takes(sink, seg, x_shape, like: Tensor) -> bool:
+    """May this term go to the sink?  The switch is on, the input is a [B, T, S, d] device tensor, and bist_gemm_kseg takes the
+    segment (else the term is launched as a product of its own, as before)."""
+    if sink is None or not _seg_on() or len(x_shape) != 4 or not like.is_cuda:
+        return False
+    B, T, S, d = x_shape
+    # (`like` stands in for the output, which does not exist yet: only its dtype is looked at, allocations are 16-byte aligned)
+    return like.data_ptr() % 16 == 0 and ops.gemm_kseg_ok([seg], like, M=T * S, N=d, ldc=d, batch=(B, 1), c_bs=(T * S * d, 0))
+
+
 def _mask_u8(mask: Optional[Tensor]):
     if mask is None:
         return None
@@ -126,6 +187,7 @@ class LinearFn(Function):
     @staticmethod
     def forward(ctx, x, w, bias, residual, act, res_map, alpha, drop_p, drop_seed, out_dtype, out_shape=None, leaf=False):
         ctx.leaf = bool(leaf)
+        ctx.sink = getattr(x, "_bist_sink", None) if leaf else None      # x is an alias of a fanned-out tensor (the video tensor)
         K = x.shape[-1]
         ln = getattr(x, "_bist_ln", None)              # x is a pending LayerNorm output: this product normalises the rows itself and fills x
         if ln is not None:
@@ -195,6 +257,16 @@ class LinearFn(Function):
                                         _ptr(ops.DROP_CTR) if drop_p > 0 else None, dtype_code(dz.dtype), _stream()),
                   "bist_epilogue_bwd")
             dz = dz2
+        if ctx.leaf and ctx.gate is None and ctx.sink is not None and ctx.needs_input_grad[0] and dz.is_contiguous():
+            seg = _value_seg(dz, w, x_shape[1] * x_shape[2] if len(x_shape) == 4 else 0)
+            if _seg_takes(ctx.sink, seg, x_shape, dz):
+                # dX = alpha dZ.W is one of the video tensor's gradient terms: left to FanOutFn's K-segmented launch; dW / db as ever
+                with _Leaf(x2, w, dz, on=ops.LEAF_STREAM is not None and bool(ops.LEAF_MASK & 1)):
+                    _, dw, db = _linear_grads(x2, w, dz, alpha, ctx.w_dst, ctx.b_dst, bias_dtype if has_bias else None,
+                                              False, ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2])
+                w_ = _weight_now(w)
+                _seg_push(ctx.sink, "value", _value_seg(dz, w_, x_shape[1] * x_shape[2]), alpha, (dz, w_))
+                return _seg_placeholder(x_shape, dz, ctx.sink), dw, db, dres, None, None, None, None, None, None, None, None
         if ctx.leaf and ctx.gate is None and ops.LEAF_STREAM is not None and (ops.LEAF_MASK & 1):
             # a projection of the video tensor (the stage-1 values): both backward products are leaves -- dX is one of the video tensor's
             # gradients (FanOutFn sums them at the end), dW accumulates into the flat gradient
@@ -773,16 +845,28 @@ class FanOutFn(Function):
     [B*T*S, d] gradient; the encoded texts feed every decoder layer."""
 
     @staticmethod
-    def forward(ctx, x, n, join=False):
+    def forward(ctx, x, n, join=False, sink=None):
         ctx.n = n
         ctx.join = bool(join)
+        ctx.sink = sink                         # functional.Fan tags every alias with it (after apply: attributes set here do not survive)
         ctx.set_materialize_grads(False)        # aliases nobody read carry no gradient: None, not a zero tensor autograd would fill and we would sum
         return tuple(x.view_as(x) for _ in range(n))
 
     @staticmethod
     def backward(ctx, *grads):
         gs = [g for g in grads if g is not None]
-        if ctx.join and len(gs) > 1 and gs[0].is_cuda:
+        sink = ctx.sink
+        pending = list(sink) if sink else []
+        if sink:
+            del sink[:]
+        marked = sum(1 for g in gs if getattr(g, "_bist_seg", None) is sink and sink is not None)
+        if pending or marked:
+            if marked != len(pending):
+                raise RuntimeError("bist_amd: %d gradient terms of a fanned-out tensor were left to its K-segmented sum, but %d marked "
+                                   "placeholders arrived (a hook, retain_grad or a view on an alias re-wrapped one: an UNINITIALISED "
+                                   "placeholder would be summed as a gradient) -- set BIST_VIDEO_GRAD_SEG=0 for such graphs" % (len(pending), marked))
+            gs = [g for g in gs if getattr(g, "_bist_seg", None) is not sink]
+        if ctx.join and len(gs) + len(pending) > 1 and grads and any(g is not None and g.is_cuda for g in grads):
             # join=True (a fan made on the MAIN stream whose consumers run on the side streams too): the sum waits for the present position of
             # every side stream.  The engine orders a gradient behind its producing NODE's stream; measured with a fan for encoded_tgt, that
             # did not cover a gradient arriving from the caption stream in the replayed step (it ran 0.4 ms faster and updated unrelated
@@ -797,13 +881,46 @@ class FanOutFn(Function):
             ev = getattr(g, "_bist_ready", None)
             if ev is not None:
                 torch.cuda.current_stream().wait_event(ev)
+        if pending:
+            return _segment_sum(pending, gs, next(g for g in grads if g is not None)), None, None, None
         if not gs:
-            return None, None, None
+            return None, None, None, None
         if len(gs) == 1:
-            return gs[0], None, None
+            return gs[0], None, None, None
         if len({g.dtype for g in gs}) > 1:
             gs = [g.to(gs[0].dtype) for g in gs]
-        return ops.add_n(gs), None, None
+        return ops.add_n(gs), None, None, None
+
+
+def _segment_sum(pending, gs, like: Tensor) -> Tensor:
+    """The sum of the pending segment terms (and of the gradients `gs` that arrived as tensors) of a [B, T, S, d] tensor: one
+    bist_gemm_kseg launch per (operand layout, alpha) group in order of first appearance, each group adding to the previous one's
+    output through the residual -- in the output dtype, so the bf16 sum is rounded once per group (twice for the video tensor: score
+    terms, value terms), not once per term.  Runs on the current stream (FanOutFn's) after the events the producers recorded."""
+    B, T, S, d = like.shape
+    TS = T * S
+    cur = torch.cuda.current_stream()
+    for _, _, _, ev, _ in pending:
+        cur.wait_event(ev)
+    dt = pending[0][1][0].dtype
+    out = torch.empty((B, T, S, d), device=like.device, dtype=dt)
+    res = None
+    if gs:
+        gs = [g if g.dtype == dt else g.to(dt) for g in gs]
+        res = ops.add_n(gs) if len(gs) > 1 else gs[0].contiguous()
+    groups = {}
+    for kind, seg, alpha, _, keep in pending:
+        groups.setdefault((kind, alpha), []).append(seg)
+    for (kind, alpha), segs in groups.items():
+        ops.gemm_kseg(segs, out, M=TS, N=d, ldc=d, batch=(B, 1), c_bs=(TS * d, 0), alpha=alpha,
+                      residual=res, ldr=d, r_bs=(TS * d, 0))
+        res = out
+    for _, _, _, _, keep in pending:          # operands of another stream's pool, read here: the allocator holds them until this stream is past
+        for t in keep:
+            t.record_stream(cur)
+    if ops.WGRAD_KEEP_OWNED:                  # a trainer's pass (possibly a capture): it also holds them until it has joined the streams
+        ops.WGRAD_KEEP.append(tuple(t for p_ in pending for t in p_[4]) + (out,))
+    return out
 
 
 class CastFn(Function):
@@ -930,6 +1047,7 @@ class St1FusedTrainFn(Function):
         y, v, p, o = ops.st_stage1_fused_train(qf.reshape(B, -1, d), vft_a, m8, wv_frag, bv, wo_frag, bo, x, h=h, direction=direction,
                                                attn_drop=adrop, sub_drop=sdrop, want_v=v_in is None)
         ctx.own_v = v_in is None
+        ctx.sinks = (getattr(vft_a, "_bist_sink", None), getattr(vft_b, "_bist_sink", None) if vft_b is not None else None)
         ctx.save_for_backward(qf, vft_a, v if v_in is None else v_in, p, o, m8, wv, wo)
         ctx.cfg = (cfg, tuple(x.shape), bv.dtype, tuple(qf.shape))
         ctx.w_dst = (getattr(wv, "_grad_view", None), getattr(wo, "_grad_view", None))
@@ -982,7 +1100,6 @@ class St1FusedTrainFn(Function):
             if Fn_.CONCURRENT:
                 side = Fn_.side_stream(1)
         o2 = o.view(M, d)
-        dvft_a = torch.empty((B, TS, d), device=dev, dtype=dt)          # (escapes: allocated on this stream's pool)
         if side is None:
             do, dwo, dbo = _linear_grads(o2, wo, dz, 1.0, ctx.w_dst[1], ctx.b_dst[1], bdt, True, ctx.needs_input_grad[8], ctx.needs_input_grad[9])
         else:
@@ -997,28 +1114,51 @@ class St1FusedTrainFn(Function):
         ops.gemm(dsc, vf, dqf, M=R, N=d, K=TS, a_rs=TS, a_ks=1, b_rs=1, b_ks=vf.stride(1), ldc=d, batch=(B, 1),
                  a_bs=(R * TS, 0), b_bs=(vf.stride(0), 0), c_bs=(R * d, 0))
 
+        # the video tensor's gradient through the scores, dsc^T.Qf: left to the K-segmented sum of the tensor's fan when the alias carries
+        # a sink (FanOutFn forms all terms in one launch per operand layout), else a product of its own
+        seg_a = _score_seg(dsc, q3, B, R, TS)
+        sunk_a = _seg_takes(ctx.sinks[0], seg_a, tuple(vft.shape), dsc)
+        dvft_a = None if sunk_a else torch.empty((B, TS, d), device=dev, dtype=dt)          # (escapes: allocated on this stream's pool)
+
         def video_grad():
-            ops.gemm(dsc, q3, dvft_a, M=TS, N=d, K=R, a_rs=1, a_ks=TS, b_rs=1, b_ks=q3.stride(1), ldc=d, batch=(B, 1),
-                     a_bs=(R * TS, 0), b_bs=(q3.stride(0), 0), c_bs=(TS * d, 0))
+            if not sunk_a:
+                ops.gemm(dsc, q3, dvft_a, M=TS, N=d, K=R, a_rs=1, a_ks=TS, b_rs=1, b_ks=q3.stride(1), ldc=d, batch=(B, 1),
+                         a_bs=(R * TS, 0), b_bs=(q3.stride(0), 0), c_bs=(TS * d, 0))
+        ev = None
         if side is None:
             video_grad()
         else:
             cur = torch.cuda.current_stream()
             side.wait_stream(cur)
-            ops.WGRAD_KEEP.append((dz, o2, dsc, q3, dvft_a))
-            for t_ in (dz, o2, dsc, q3, dvft_a):
+            keep_ = (dz, o2) if sunk_a else (dz, o2, dsc, q3, dvft_a)
+            ops.WGRAD_KEEP.append(keep_)
+            for t_ in keep_:
                 t_.record_stream(side)              # read / written by the side stream after this call has released them
             with torch.cuda.stream(side):
                 _linear_grads(o2, wo, dz, 1.0, ctx.w_dst[1], ctx.b_dst[1], bdt, False, True, ctx.needs_input_grad[9])
                 video_grad()
-                ev = torch.cuda.Event()
-                ev.record(side)
-            dvft_a._bist_ready = ev
-        gva = dvft_a.view(vft.shape)
-        if getattr(dvft_a, "_bist_ready", None) is not None:
-            gva._bist_ready = dvft_a._bist_ready
+                if not sunk_a:
+                    ev = torch.cuda.Event()
+                    ev.record(side)
+        if sunk_a:
+            _seg_push(ctx.sinks[0], "score", seg_a, 1.0, (dsc, q3))
+            gva = _seg_placeholder(vft.shape, dsc, ctx.sinks[0])
+        else:
+            gva = dvft_a.view(vft.shape)
+            if ev is not None:
+                gva._bist_ready = ev
         if not ctx.own_v:            # the value projection is a product of its own (another stream): its backward takes dV from here
             return (dqf.view(qf_shape), dres.view(x_shape), gva, None, dv, None, None, None, dwo, dbo, None, None, None)
+        dv2 = dv.view(B * TS, d)
+        seg_b = _value_seg(dv2, wv, TS)
+        if _seg_takes(ctx.sinks[1], seg_b, tuple(vft.shape), dv2):      # the value projection's dX: a segment of the same sum
+            with _Leaf(vft, wv, dv, on=bool(ops.LEAF_MASK & 1)):
+                _, dwv, dbv = _linear_grads(vft.view(B * TS, d), wv, dv2, 1.0, ctx.w_dst[0], ctx.b_dst[0], bdt, False,
+                                            ctx.needs_input_grad[6], ctx.needs_input_grad[7])
+            wv_ = _weight_now(wv)
+            _seg_push(ctx.sinks[1], "value", _value_seg(dv2, wv_, TS), 1.0, (dv, wv_))
+            gvb = _seg_placeholder(vft.shape, dv, ctx.sinks[1])
+            return (dqf.view(qf_shape), dres.view(x_shape), gva, gvb, None, None, dwv, dbv, dwo, dbo, None, None, None)
         with _Leaf(vft, wv, dv, on=bool(ops.LEAF_MASK & 1)) as lf:        # the launch projected the values itself: the projection's two backward products are leaves too
             dvft_b, dwv, dbv = _linear_grads(vft.view(B * TS, d), wv, dv.view(B * TS, d), 1.0, ctx.w_dst[0], ctx.b_dst[0], bdt, True,
                                              ctx.needs_input_grad[6], ctx.needs_input_grad[7])

@@ -367,12 +367,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   bf16_t* dt = ptr + KPAD * PP;                                  // [32][DK]
   bf16_t* stage = ptr;                                           // [KPAD][DK], after both are consumed
   // ---- loads: the dO tile into LDS, V fragments and probabilities into registers ----------------------------------------
+  // (every load of this batch is unconditional -- rows and keys past the end are clamped to the last valid one and zeroed / ignored after
+  // the wait -- so the four dO pieces and the mask bytes go out back to back with the V fragments and the probabilities: section 16's rule)
   const bf16_t* dOb = a.dO + (((long)b * G + g) * Lq) * d + hh * DK;
-  for (int i = lane >> 3; i < 32; i += 8) {
-    uint4 q = make_uint4(0u, 0u, 0u, 0u);
-    if (i < Lq) q = *reinterpret_cast<const uint4*>(dOb + (long)i * d + (lane & 7) * 8);
-    *reinterpret_cast<uint4*>(dt + i * DK + (lane & 7) * 8) = q;
-  }
+  uint4 dq[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) dq[t] = *reinterpret_cast<const uint4*>(dOb + (long)min((lane >> 3) + 8 * t, Lq - 1) * d + (lane & 7) * 8);
+  const unsigned char* mk = a.tmask ? a.tmask + (long)b * Kn : nullptr;
+  const unsigned char* mkp = mk ? mk : reinterpret_cast<const unsigned char*>(dOb);      // no mask: any valid byte, value ignored
+  unsigned char mkb[NKF];
+#pragma unroll
+  for (int ni = 0; ni < NKF; ++ni) mkb[ni] = mkp[mk ? min(ni * 16 + x, Kn - 1) : 0];
   const bf16_t* Vb = a.V + (long)b * TS_ * a.ldv + hh * DK;
   uint4 vf[2][NKF];
 #pragma unroll
@@ -396,6 +401,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         pv[mi][r][ni] = (i < Lq && k < Kn) ? Pg[(long)i * a.p_kp + k] : 0.f;
       }
     }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int i = (lane >> 3) + 8 * t;
+    *reinterpret_cast<uint4*>(dt + i * DK + (lane & 7) * 8) = i < Lq ? dq[t] : make_uint4(0u, 0u, 0u, 0u);
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   // ---- dP = dO . V^T ------------------------------------------------------------------------------------------------------
@@ -417,14 +427,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // ---- dS, and the P'^T image ---------------------------------------------------------------------------------------------
   const unsigned long long dkey = a.drop.p > 0.f ? a.drop.key() : 0ULL;
   const float dks = a.drop.p > 0.f ? a.drop.keep_scale() : 1.f;
-  const unsigned char* mk = a.tmask ? a.tmask + (long)b * Kn : nullptr;
   float* dsc = reinterpret_cast<float*>(a.dscores) + (long)b * Lq * h * TS_;
   bf16_t* dsc16 = reinterpret_cast<bf16_t*>(a.dscores) + (long)b * Lq * h * TS_;
   unsigned keym = 0u;                                            // bit ni: key ni * 16 + x is live (inside the range and not masked)
 #pragma unroll
   for (int ni = 0; ni < NKF; ++ni) {
     const int k = ni * 16 + x;
-    if (k < Kn && !(mk && mk[k] == 0)) keym |= 1u << ni;
+    if (k < Kn && !(mk && mkb[ni] == 0)) keym |= 1u << ni;
   }
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) {

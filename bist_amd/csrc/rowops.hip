@@ -329,6 +329,7 @@ extern "C" int bist_add_n(const void* const* srcs, int32_t n, void* out, int64_t
     hipLaunchKernelGGL(add_n_kernel<float>, dim3(blocks_for((numel + 3) / 4, 256)), dim3(256), 0, st, p, n, (float*)out, (long)numel);
   else { bist_set_error("bist_add_n: bad dtype %d", dtype); return BIST_EINVAL; }
   BIST_LAUNCH_CHECK("bist_add_n");
+  bist_count_launch(BIST_K_ADD_N);
   return BIST_OK;
 }
 

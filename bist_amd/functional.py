@@ -219,7 +219,17 @@ class Fan:
 
     def __init__(self, x, n: int, join: bool = False):
         self.x = x
-        self._it = iter(ag.FanOutFn.apply(x, n, join)) if (n > 1 and _grad() and x.requires_grad and x.is_cuda) else iter(())
+        outs = ()
+        if n > 1 and _grad() and x.requires_grad and x.is_cuda:
+            # the fan's sink: a consumer whose gradient for its alias is a product onto the same rows (the video tensor's score and value
+            # terms) leaves the operands there, and the fan's backward forms all of them in one K-segmented launch per operand layout
+            # (autograd._Sink).  Tagged HERE: attributes set inside forward on views of an input do not reliably survive apply.
+            sink = ag._Sink() if x.dim() == 4 else None
+            outs = ag.FanOutFn.apply(x, n, join, sink)
+            if sink is not None:
+                for a in outs:
+                    a._bist_sink = sink
+        self._it = iter(outs)
 
     def take(self):
         return _keep_taken(next(self._it, self.x))

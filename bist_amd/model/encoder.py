@@ -327,7 +327,9 @@ class VidEncoderLayer4(nn.Module):
     def train_value(self, vft_a: Tensor, ai: int):
         B, T, S, d = vft_a.shape
         a = self.attn[ai]
-        return Fn.linear(vft_a.view(B * T * S, d), a.linears[2].weight, a.linears[2].bias, leaf=True).view(B, T, S, d)
+        # (the alias goes in as it was handed out, and both shapes are made inside the node: a view node on either side would re-wrap
+        # the gradient tensors and drop what travels on them -- the fan's sink tag forward, the segment placeholder backward)
+        return Fn.linear(vft_a, a.linears[2].weight, a.linears[2].bias, leaf=True, out_shape=(B, T, S, d))
 
     def train_values(self, vft_a: Tensor, vft_b: Tensor):
         """Training: one value GEMM per direction (each dV is a whole tensor) -> (v_t2s, v_s2t)."""

@@ -256,14 +256,87 @@ def gemm(a: Tensor, b: Tensor, c: Tensor, **kw) -> Tensor:
 
 WGRAD_STREAM = None       # trainer: side stream of the weight-gradient GEMMs (autograd._WeightGradStream); None = in line
 WGRAD_KEEP = []           # their operands, kept alive until the trainer joins that stream
+WGRAD_KEEP_OWNED = False  # a trainer is inside its backward pass and clears WGRAD_KEEP at the join (nothing else may append without a stream of its own)
 LEAF_STREAM = None        # trainer: the stream of the backward pass's leaf products (autograd._Leaf); None = in line
 LEAF_MASK = 0             # which leaves go there (bist_amd/train.py: LEAF_MASK)
+# trainer: parameters are updated INSIDE the backward pass (the early buckets of a captured step).  A gradient term left to FanOutFn's
+# K-segmented sum is formed at the END of the pass, so a term that reads a weight takes a copy of it where the product used to run
+SEG_SNAPSHOT_W = False
 def gemm_pair(ga: BistGemm, gb: BistGemm) -> None:
     """Two independent products (descriptors from gemm_desc) in one call; one launch when they are the small dX / dW
     pair of a linear layer's backward (bist_gemm_pair)."""
     _refuse_split64(ga)
     _refuse_split64(gb)
     check(lib.bist_gemm_pair(C.byref(ga), C.byref(gb), _stream()), "bist_gemm_pair")
+
+
+GEMM_KSEG_MAX = _lib.GEMM_KSEG_MAX
+
+
+def kseg(a: Tensor, b: Tensor, K: int, *, a_rs: int, b_rs: int, a_ks: int = 1, b_ks: int = 1,
+         a_bs: Tuple[int, int] = (0, 0), b_bs: Tuple[int, int] = (0, 0), a_off: int = 0, b_off: int = 0):
+    """One segment A_s . B_s^T of a K-segmented product (gemm_kseg): operands, element strides and batch strides as in gemm_desc."""
+    return (a, b, int(K), int(a_rs), int(a_ks), tuple(a_bs), int(b_rs), int(b_ks), tuple(b_bs), int(a_off), int(b_off))
+
+
+def gemm_kseg_desc(segs, c: Tensor, *, M: int, N: int, ldc: int, residual: Optional[Tensor] = None, ldr: int = 0, alpha: float = 1.0,
+                   batch: Tuple[int, int] = (1, 1), c_bs: Tuple[int, int] = (0, 0), r_bs: Tuple[int, int] = (0, 0),
+                   c_off: int = 0, r_off: int = 0) -> _lib.BistGemmKSeg:
+    """Descriptor of C = alpha * sum_s A_s.B_s^T (+ residual) for at most GEMM_KSEG_MAX segments (include/bist_hip.h: BistGemmKSeg)."""
+    if not 1 <= len(segs) <= GEMM_KSEG_MAX:
+        raise ValueError(f"bist_amd.gemm_kseg: 1..{GEMM_KSEG_MAX} segments per launch")
+    dt = segs[0][0].dtype
+    _dev(c, residual)
+    if residual is not None and residual.dtype != c.dtype:
+        raise TypeError("bist_amd.gemm_kseg: residual dtype must equal the output dtype")
+    g = _lib.BistGemmKSeg()
+    g.C, g.residual = _ptr(c, c_off), _ptr(residual, r_off)
+    g.M, g.N, g.ldc, g.ldr = M, N, ldc, ldr
+    g.batch1, g.batch2 = batch
+    g.c_bs1, g.c_bs2 = c_bs
+    g.r_bs1, g.r_bs2 = r_bs
+    g.alpha = alpha
+    g.in_dtype, g.out_dtype = dtype_code(dt), dtype_code(c.dtype)
+    g.nseg = len(segs)
+    for i, (a, b, K, a_rs, a_ks, a_bs, b_rs, b_ks, b_bs, a_off, b_off) in enumerate(segs):
+        _dev(a, b)
+        if a.dtype != dt or b.dtype != dt:
+            raise TypeError("bist_amd.gemm_kseg: every operand of a launch has one dtype")
+        s = g.seg[i]
+        s.A, s.B, s.K = _ptr(a, a_off), _ptr(b, b_off), K
+        s.a_rs, s.a_ks, (s.a_bs1, s.a_bs2) = a_rs, a_ks, a_bs
+        s.b_rs, s.b_ks, (s.b_bs1, s.b_bs2) = b_rs, b_ks, b_bs
+    return g
+
+
+def gemm_kseg_ok(segs, c: Tensor, **kw) -> bool:
+    """Would gemm_kseg run these segments as ONE launch of the K-segmented kernel (bist_gemm_kseg_ok)?"""
+    if not segs or len(segs) > GEMM_KSEG_MAX or not all(s[0].is_cuda and s[1].is_cuda for s in segs) or not c.is_cuda:
+        return False
+    return bool(lib.bist_gemm_kseg_ok(C.byref(gemm_kseg_desc(segs, c, **kw))))
+
+
+def gemm_kseg(segs, c: Tensor, *, M: int, N: int, ldc: int, residual: Optional[Tensor] = None, ldr: int = 0, alpha: float = 1.0,
+              batch: Tuple[int, int] = (1, 1), c_bs: Tuple[int, int] = (0, 0), r_bs: Tuple[int, int] = (0, 0)) -> Tensor:
+    """C = alpha * sum_s A_s.B_s^T (+ residual), segments from kseg().  One launch per GEMM_KSEG_MAX segments with the fp32 sum kept in
+    registers and rounded once; a longer list chains through the residual (C itself: every output element is read and written by one
+    lane).  Segments the K-segmented kernel refuses (bist_gemm_kseg_ok: alignment, whole 16-byte pieces, mixed layouts) run as
+    bist_gemm products of their own, chained the same way."""
+    segs = list(segs)
+    kw = dict(M=M, N=N, ldc=ldc, alpha=alpha, batch=batch, c_bs=c_bs)
+    res, rkw = residual, dict(ldr=ldr, r_bs=r_bs)
+    for o in range(0, len(segs), GEMM_KSEG_MAX):
+        part = segs[o:o + GEMM_KSEG_MAX]
+        g = gemm_kseg_desc(part, c, residual=res, **kw, **rkw)
+        if lib.bist_gemm_kseg_ok(C.byref(g)):
+            check(lib.bist_gemm_kseg(C.byref(g), _stream()), "bist_gemm_kseg")
+            res, rkw = c, dict(ldr=ldc, r_bs=c_bs)
+        else:
+            for (a, b, K, a_rs, a_ks, a_bs, b_rs, b_ks, b_bs, a_off, b_off) in part:
+                gemm(a, b, c, K=K, a_rs=a_rs, a_ks=a_ks, a_bs=a_bs, b_rs=b_rs, b_ks=b_ks, b_bs=b_bs, a_off=a_off, b_off=b_off,
+                     residual=res, **kw, **rkw)
+                res, rkw = c, dict(ldr=ldc, r_bs=c_bs)
+    return c
 
 
 COLSUM_QUEUE = None       # trainer: list of (dz, acc32 view, M, N) bias-gradient jobs, flushed by col_sum_flush()

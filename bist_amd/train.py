@@ -637,6 +637,8 @@ class Trainer:
         # the split executor (a fourth stream in a graph for the runtime's executor is not trusted: Fn.MAX_CAPTURE_STREAMS)
         ops.LEAF_STREAM = Fn.leaf_stream() if (LEAF_OFFLOAD and self.use_graph and SPLIT_GRAPH and loss.is_cuda and Fn.CONCURRENT) else None
         ops.LEAF_MASK = LEAF_MASK
+        ops.WGRAD_KEEP_OWNED = True
+        ops.SEG_SNAPSHOT_W = bool(early)      # the early buckets' update rewrites weights that the video gradient's deferred value terms read
         try:
             if self.overlap or early:
                 self._main_stream = torch.cuda.current_stream()
@@ -660,6 +662,8 @@ class Trainer:
             self._early_keep.clear()
             ops.WGRAD_STREAM = None
             ops.LEAF_STREAM = None
+            ops.SEG_SNAPSHOT_W = False
+            ops.WGRAD_KEEP_OWNED = False
             ops.WGRAD_KEEP.clear()
             Fn.release_taken()
         return terms

@@ -59,7 +59,9 @@ int bist_device_ok(void);
 #define BIST_K_ST1_FUSED_TRAIN 11   /* bist_st_stage1_fused_train_fwd                                        */
 #define BIST_K_ST1_PBWD 12      /* bist_st_stage1_pv_bwd_p (backward core fed with the saved probabilities)  */
 #define BIST_K_MHA_FWD_DK64 13  /* of the BIST_K_MHA_FWD launches, those of mha_core_dk64_kernel (operands fetched ahead) */
-#define BIST_K_COUNT 14
+#define BIST_K_GEMM_KSEG 14     /* bist_gemm_kseg launches (K-segmented products)                             */
+#define BIST_K_ADD_N 15         /* bist_add_n launches                                                        */
+#define BIST_K_COUNT 16
 int64_t bist_launch_count(int32_t family);
 void bist_launch_count_reset(void);
 /* Development hook: hand the fused stage-1 kernel (which = 0) or the persistent decoder kernel (which = 1) a caller-owned DEVICE
@@ -162,6 +164,41 @@ int bist_gemm_pair(const BistGemm* a, const BistGemm* b, void* stream);
  * products of 140+ such tiles, or hint BIST_GEMM_TILE256), 0 = generic strided kernel
  * (host-side query, used by tests and the bench report).                                          */
 int bist_gemm_is_fast(const BistGemm* g);
+
+/* K-segmented product:  C[z] = alpha * sum_s A_s[z] . B_s[z]^T (+ residual), one launch of the 128x128-tile kernel with the fp32
+ * accumulators kept in registers across the segments and ONE rounding at the store.  Sums gradient terms that land on the same rows
+ * -- the 24 terms of the video tensor's gradient (each (layer, direction) pair of the encoder reads it through its scores and through
+ * its value projection: encoder.py:114-121,145-148) -- where the products are formed, instead of writing each term and adding them
+ * afterwards.  Operands are addressed as in BistGemm; every segment has its own pointers, strides, batch strides and K, and all
+ * segments of one launch share M, N, the batch and the operand LAYOUTS (per operand K-contiguous or row-contiguous).  The order of
+ * additions is segment order, then K order: the result depends on the descriptor alone.  No bias, activation, dropout or split-K.
+ * bist_gemm_kseg_ok answers 1 when bist_gemm_kseg will run the descriptor: 1..BIST_GEMM_KSEG_MAX segments, each within the
+ * LDS-DMA envelope of bist_gemm (16-byte aligned bases, strides and batch strides; a K-contiguous operand needs K_s in whole 16-byte
+ * pieces, a row-contiguous one a row count in whole pieces), all with the layouts of segment 0.  Otherwise the caller runs the
+ * products one by one; bist_gemm_kseg itself returns BIST_EINVAL.                                                                */
+#define BIST_GEMM_KSEG_MAX 24
+typedef struct BistGemmSeg {
+  const void* A;
+  const void* B;
+  int64_t a_rs, a_ks, a_bs1, a_bs2;
+  int64_t b_rs, b_ks, b_bs1, b_bs2;
+  int32_t K;
+  int32_t reserved;
+} BistGemmSeg;
+typedef struct BistGemmKSeg {
+  void* C;
+  const void* residual;  /* out_dtype elements, leading dimension ldr, or NULL */
+  int32_t M, N;
+  int64_t ldc, ldr;
+  int32_t batch1, batch2;
+  int64_t c_bs1, c_bs2, r_bs1, r_bs2;
+  float alpha;
+  int32_t in_dtype, out_dtype;
+  int32_t nseg;
+  BistGemmSeg seg[BIST_GEMM_KSEG_MAX];
+} BistGemmKSeg;
+int bist_gemm_kseg_ok(const BistGemmKSeg* g);
+int bist_gemm_kseg(const BistGemmKSeg* g, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * LayerNorm of the reference:  y = a * (x - mean) / (std_unbiased + eps) + b   per row
